@@ -37,6 +37,17 @@ frame, on every core the process may use (cores stated).
 parity_vs_oracle: the GPU's 256-spp radiance against the oracle on one 8-row band (the
 metric's "RMSE vs ref @256spp"); C4 (ReSTIR DI reuses the whole frame): whole frames, as
 many as the oracle renders in its budget; C1: the whole frame at K spp.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline figure needs: scene
+set-up, one untimed wavefront (the frames of --full's calibration pass), W warmup steps, the N timed steps, and the
+line (value, ms_per_step, the timed region's own per-kernel event times).  `--full` adds every leg
+that takes runs of its own: the instrumented calibration pass and the rooflines built on it, the
+shading kernel's solo batch, the one-sample-per-wavefront leg, parity_vs_oracle, cpu_baseline and
+the other BASELINE configs (each still switchable by its own option).
+`--dump-outputs DIR` writes what the timed steps computed, right after them: DIR/color.npy, the
+float32 [rows, W, 3] radiance sums a caller reads back (mpt_get_framebuffer; on N ranks the gathered
+frame), or a seeded sample of its pixels when the frame exceeds DUMP_MAX_BYTES.  Scenes, sky and
+seed schedules are seeded, so the same arguments give the same inputs on every run and build.
 """
 import argparse
 import json
@@ -65,6 +76,8 @@ TARGET_PATHS = 64 * 1920 * 1080  # paths per wavefront launch (mpt_render_frames
 # 3.92 / 3.86 / 3.77, profiles/r06ab_c3_batch_ab.json)
 TARGET_PATHS_RESTIR = 8 * 1920 * 1080
 MAX_BATCH = 128    # MPT_MAX_BATCH
+DUMP_MAX_BYTES = 64 * 1000 * 1000    # --dump-outputs: the most it writes, file headers included
+NPY_HEADER_MAX = 1024                # room kept for a .npy file's header (128 bytes for these shapes)
 
 
 def parse():
@@ -80,6 +93,11 @@ def parse():
                     help="default: c3 ris (reference default), c2 mis")
     ap.add_argument("--bounces", type=int, default=None, help="default 3 (c5: 16)")
     ap.add_argument("--bsdf", default="principled", choices=["principled", "lambert"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: calibration + rooflines, solo shading batch, "
+                         "batch-1 leg, parity vs the oracle, CPU baseline, the other configs (default: off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the radiance sums of the timed steps to DIR/color.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU-baseline sample duration")
     ap.add_argument("--parity-spp", type=int, default=256, help="spp of the RMSE-vs-oracle band (the metric's 256)")
     ap.add_argument("--parity-seconds", type=float, default=90.0, help="oracle budget of the parity leg")
@@ -107,7 +125,10 @@ def parse():
     ap.add_argument("--emulate-rank-of", type=int, default=1,
                     help="scaling rehearsal on one GPU: render only rank 0's share of an N-way row split "
                          "(the line then reports that rank's rate; not a bench line)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 LSS = {"mis": abi.LSS_MIS_LIGHT_BSDF, "ris": abi.LSS_RIS_BSDF_AND_LIGHT, "uniform": abi.LSS_UNIFORM_ONE_LIGHT,
@@ -356,6 +377,26 @@ def emulate_restir_ranks(a, r, cam, W, H, opt, wset, alpha, n_ranks, K, device):
             "bands": bands, "device": {"libmpt_sha256_16": mpt.build_id()}}
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32).  The files share DUMP_MAX_BYTES
+    (each one's header counted as NPY_HEADER_MAX); a larger array is written as a fixed sample of its
+    pixels (rows of its [pixels, C] view, drawn without replacement by default_rng(0) and sorted),
+    the same pixels on every run.  Returns what the line reports about each file."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays) - NPY_HEADER_MAX
+    info = {}
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        info[name] = {"shape": list(arr.shape), "dtype": "float32", "sample": None}
+        if arr.nbytes > share:
+            px = arr.reshape(-1, arr.shape[-1])
+            n = share // (4 * px.shape[1])
+            arr = px[np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))]
+            info[name]["sample"] = f"{n} of {px.shape[0]} pixels (default_rng(0), sorted): shape {list(arr.shape)}"
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return info
+
+
 _SCENES = {}
 
 
@@ -389,7 +430,7 @@ def main():
         else:
             dist.init_process_group(backend)
     out = run_workload(a, world, rank, local, dist, coll_dev)
-    if out is not None and world == 1 and a.emulate_rank_of == 1 and a.configs != "none":
+    if out is not None and a.full and world == 1 and a.emulate_rank_of == 1 and a.configs != "none":
         # the other BASELINE configurations in the same line, each at a reduced budget (their
         # own spp would take minutes; a step is still one sample per pixel of the full frame)
         import copy
@@ -404,6 +445,7 @@ def main():
             b.bsdf, b.batch = "principled", 0
             b.cpu_seconds, b.parity_seconds = 5.0, 15.0
             b.batch1_steps = 0
+            b.dump_outputs = None
             t0 = time.perf_counter()
             try:
                 o = run_workload(b, world, rank, local, dist, coll_dev, quiet=True)
@@ -526,8 +568,11 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
             halo = partition.TorchHaloExchange(dist, band_h)
             r.set_halo_exchange(halo)
 
-    # calibration: instrumented traversal -> nodes / triangles per query per stage
-    r.enable_stats(timing=False, instrumented=True)
+    # calibration (--full): instrumented traversal -> nodes / triangles per query per stage; a plain
+    # run renders the same frames uninstrumented, so that its warmup and timed steps start from the
+    # context --full's do (path state allocated for a whole batch, C4's ReSTIR DI history) and the
+    # two modes compute the same images
+    r.enable_stats(timing=False, instrumented=a.full)
     # (one batch, so every launch of the run has the timed region's size)
     cal_frames = frames_for(cam, W, H, opt, band, max(2, batch), first=0, bounces=a.bounces, world=wset, alpha=alpha)
     r.render_samples(cal_frames, max_batch=batch)
@@ -559,6 +604,11 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     st = r.stats()
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # before any later leg renders into the same framebuffer
+        dumped = dump_outputs(a.dump_outputs, {"color": frame.cpu().numpy() if dist is not None
+                                               else r.framebuffer(abi.FB_COLOR)})
 
     rays_local = st.rays_closest + st.rays_any
     if dist is not None:
@@ -574,7 +624,7 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
     # launch latency: the same frames with one sample per wavefront (the launch set of
     # mpt_render_frame, ~50 launches per sample) against the batched wavefronts timed above
     batch1 = None
-    if a.workload == "c3" and world == 1 and band[2] == 1 and getattr(a, "batch1_steps", 0) > 0:
+    if a.full and a.workload == "c3" and world == 1 and band[2] == 1 and getattr(a, "batch1_steps", 0) > 0:
         n1 = a.batch1_steps
         fr1 = frames_for(cam, W, H, opt, band, n1, bounces=a.bounces, world=wset, alpha=alpha)
         r.enable_stats(timing=False, instrumented=False)
@@ -594,7 +644,7 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
     # the GPU; one more batch of the same frames with the bounces in line (untimed for `value`,
     # same images) gives the kernel's own launch time (the roofline's `solo`)
     solo = None
-    if st.pipelined_batches and not a.no_solo:
+    if a.full and st.pipelined_batches and not a.no_solo:
         r.set_pipeline(0)
         fr_s = frames_for(cam, W, H, opt, band, batch, bounces=a.bounces, world=wset, alpha=alpha)
         r.synchronize_kernel()
@@ -608,7 +658,9 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
                 "shade_units_per_launch": hits_s / max(1, sts.shade_launches), "steps": batch}
 
     # rooflines (SURVEY.md §8d algorithmic bytes): every traversal stage and the shade
-    # kernel; "roofline" is the one with the largest summed time in the timed region
+    # kernel; "roofline" is the one with the largest summed time in the timed region.  (Reported by
+    # --full alone: a plain run's `cal` counts no nodes or triangles, and of these lines its report
+    # takes only the ReSTIR DI passes', whose bytes per pixel are the model's.)
     names = ["k_trace<TM_PATH> (camera/continuation rays, closest hit)", "k_trace<TM_NEE_ANY> (NEE shadow rays, any hit)",
              "k_trace<TM_NEE_LIGHT> + <TM_NEE_LIGHT_OCC> (NEE BSDF light-hit rays: light BVH, then whole-scene any-hit check)"]
     symbols = ["void mpt::k_trace<0, false>(mpt::TraceArgs)", "void mpt::k_trace<1, false>(mpt::TraceArgs)",
@@ -694,7 +746,7 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
     dom = max(lines[:n_kernel_lines], key=lambda x: x["total_ms"])
 
     default_cfg = a.strategy is None and default_bounces and default_bsdf and a.scene is None
-    pmc = load_traffic(a.workload, W, H) if default_cfg else None
+    pmc = load_traffic(a.workload, W, H) if default_cfg and a.full else None
 
     def pmc_entry(sym):
         if not pmc:
@@ -780,14 +832,14 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
     device = {"name": dname, "arch": darch, "compute_units": dcus, "libmpt_sha256_16": mpt.build_id()}
 
     parity = None
-    if rank == 0 and world == 1 and not a.no_parity:
+    if a.full and rank == 0 and world == 1 and not a.no_parity:
         # the GPU leg: a fresh accumulation restarting at sample 0 (sample 0 overwrites the sums)
         parity = parity_check(r, sd, luts, cam, W, H, opt, a.bounces, K if a.workload == "c1" else a.parity_spp,
                               a.workload, env=env, world=wset, alpha=alpha, max_s=a.parity_seconds, batch=batch,
                               history=cal_frames + warm_frames + frames)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             cpu = cpu_baseline(sd, luts, cam, W, H, opt, a.bounces, a.cpu_seconds, env=env, world=wset, alpha=alpha)
         except Exception as e:  # the baseline is reported, never the product path
@@ -822,20 +874,9 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
                                      f"({'libmpt native' if a.halo == 'native' else 'torch.distributed'}), RCCL all_gather"
                                      if a.workload == "c4" and world > 1 else
                                      f"interleaved {BAND_H}-row bands over {world} rank(s), RCCL all_gather")},
-            "roofline": roof(dom),
-            "roofline_traversal": roof(max(lines[:3], key=lambda x: x["total_ms"])),
-            "roofline_restir": roof(lines[n_kernel_lines - 1]) if st.restir_eval_launches else None,
-            # every timed kernel line of this run (tools/pmc_traffic.py normalises the profile of
-            # this command by them: the last `launches` dispatches of `symbol` are the timed ones)
-            "kernel_lines": [{"symbol": x["symbol"], "launches": x["launches"], "units_per_launch": x["units_per_launch"],
-                              "avg_launch_ms": round(x["avg_launch_ms"], 5), "bytes_per_unit": round(x["bytes_per_unit"], 2)}
-                             for x in lines[:n_kernel_lines]],
             "restir_passes": [{"kernel": x["kernel"], "ms_per_step": round(x["total_ms"] / K, 4), "model_bytes_per_pixel": x["bytes_per_unit"],
                                "model_achieved_gbs": round(x["achieved"], 2)} for x in lines[n_kernel_lines:]] or None,
             "device": device,
-            "traversal_stages": [{"kernel": x["kernel"].split(" ")[0], "nodes_per_ray": round(x["nodes_per_ray"], 3),
-                                  "tris_per_ray": round(x["tris_per_ray"], 3), "node_simd_util": round(x["node_simd_util"], 3),
-                                  "tri_simd_util": round(x["tri_simd_util"], 3)} for x in lines[:3]],
             "kernel_ms_per_step": {"trace_path": round(st.stage_ms[0] / K, 4), "trace_nee_any": round(st.stage_ms[1] / K, 4),
                                    "trace_nee_closest": round(st.stage_ms[2] / K, 4), "shade": round(st.shade_ms / K, 4),
                                    "shade_generic": round(st.shade_generic_ms / K, 4),
@@ -847,9 +888,28 @@ def run_workload(a, world, rank, local, dist, coll_dev, quiet=False):
                                                       enumerate(["gbuffer", "presample", "initial", "temporal_reuse",
                                                                  "spatial_reuse"])},
                                    "frame_gpu": round(st.frame_ms / max(1, st.frames), 4)},
-            "cpu_baseline": cpu,
-            "parity_vs_oracle": parity,
+            "full": a.full,
         }
+        if a.full:
+            # what needs the calibration pass (nodes / triangles per ray) or the oracle: a plain
+            # run's line says nothing about them
+            out.update({
+                "roofline": roof(dom),
+                "roofline_traversal": roof(max(lines[:3], key=lambda x: x["total_ms"])),
+                "roofline_restir": roof(lines[n_kernel_lines - 1]) if st.restir_eval_launches else None,
+                # every timed kernel line of this run (tools/pmc_traffic.py normalises the profile of
+                # this command by them: the last `launches` dispatches of `symbol` are the timed ones)
+                "kernel_lines": [{"symbol": x["symbol"], "launches": x["launches"], "units_per_launch": x["units_per_launch"],
+                                  "avg_launch_ms": round(x["avg_launch_ms"], 5),
+                                  "bytes_per_unit": round(x["bytes_per_unit"], 2)} for x in lines[:n_kernel_lines]],
+                "traversal_stages": [{"kernel": x["kernel"].split(" ")[0], "nodes_per_ray": round(x["nodes_per_ray"], 3),
+                                      "tris_per_ray": round(x["tris_per_ray"], 3), "node_simd_util": round(x["node_simd_util"], 3),
+                                      "tri_simd_util": round(x["tri_simd_util"], 3)} for x in lines[:3]],
+                "cpu_baseline": cpu,
+                "parity_vs_oracle": parity,
+            })
+        if dumped is not None:
+            out["outputs"] = {"dir": a.dump_outputs, "files": dumped}
         if batch1 is not None:
             out["batch1"] = batch1
         if st.pipelined_batches or st.trace_ahead_launches:

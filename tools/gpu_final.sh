@@ -3,7 +3,7 @@
 # rehearsal at the driver's 20 steps; outputs under gpurun_out/<tag>
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 o=gpurun_out/${1:-final}; mkdir -p $o
-timeout -k 10 400 python -u bench.py > $o/bench_default.json 2> $o/bench_default.err || { tail -20 $o/bench_default.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $o/bench_default.json 2> $o/bench_default.err || { tail -20 $o/bench_default.err; exit 1; }
 python -c "
 import json; d = json.load(open('$o/bench_default.json'))
 print('c3', d['value'], d['ms_per_step'], d['roofline']['frac'], (d['roofline'].get('solo') or {}).get('frac'), d['roofline'].get('traffic_same_library'), d.get('batch1', {}).get('ms_per_step'))

@@ -6,7 +6,7 @@ timeout -k 10 900 python -u -m pytest -q -x --durations=25 --timeout 300 --timeo
 tail -3 $o/pytest.log
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1 || { tail -5 $o/smoke.log; exit 1; }
 cat $o/smoke.log
-timeout -k 10 400 python -u bench.py > $o/bench_default.json 2> $o/bench_default.err || { tail -20 $o/bench_default.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $o/bench_default.json 2> $o/bench_default.err || { tail -20 $o/bench_default.err; exit 1; }
 python -c "
 import json; d = json.load(open('$o/bench_default.json'))
 print('c3', d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('batch1'))
