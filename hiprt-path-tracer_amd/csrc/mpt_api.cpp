@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "bvh8.h"
+#include "display.h"
 #include "mpt.h"
 #include "mpt_internal.h"
 
@@ -308,6 +309,12 @@ struct MptContext {
     // would run beside): the next ReSTIR DI batch does not overlap it
     bool as_reset_pending = false;
     DBuf<uint8_t> comm_send, comm_recv;
+    // mpt_display: a frame has been rendered into the current partition's buffers, whether the
+    // last one had the adaptive-sampling buffers (has_adaptive), the staging of a host
+    // destination and of a host second buffer
+    bool rendered = false, last_adaptive = false;
+    DBuf<uint32_t> disp_out;
+    DBuf<float> disp_second;
 };
 
 namespace {
@@ -552,6 +559,7 @@ int ensure_paths(MptContext* c, int rx, int ry, int bh, int bi, int bc) {
     HIPCHK(drain(c));
     release_batch(c);                       // sized for the previous partition
     c->res_x = c->res_y = c->n_slots = 0;   // no partition until the group below is complete
+    c->rendered = false;
     c->as_bound = 1 << 30;
     const size_t N = (size_t)std::max(n, 1);
     hipStream_t st = c->stream;
@@ -929,11 +937,11 @@ const char* mpt_last_error(void) { return g_err.c_str(); }
 int mpt_version(void) { return 1; }
 
 int mpt_abi_sizes(int32_t* out, int n) {
-    int32_t s[7] = {(int32_t)sizeof(MptMaterial), (int32_t)sizeof(MptRenderSettings), (int32_t)sizeof(MptWorldSettings),
+    int32_t s[8] = {(int32_t)sizeof(MptMaterial), (int32_t)sizeof(MptRenderSettings), (int32_t)sizeof(MptWorldSettings),
                     (int32_t)sizeof(MptCamera), (int32_t)sizeof(MptFrame), (int32_t)sizeof(MptScene),
-                    (int32_t)sizeof(MptStats)};
+                    (int32_t)sizeof(MptStats), (int32_t)sizeof(MptDisplaySettings)};
     if (!out) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    for (int i = 0; i < n && i < 7; i++) out[i] = s[i];
+    for (int i = 0; i < n && i < 8; i++) out[i] = s[i];
     return MPT_OK;
 }
 
@@ -1844,6 +1852,8 @@ static int launch_batch(MptContext* c, const MptFrame* f, int batch) {
     }
     c->frames_submitted++;
     c->frames += batch;
+    c->rendered = true;
+    c->last_adaptive = has_adaptive(f[batch - 1]);
     c->as_reset_pending = false;
     for (int k = 0; k < batch; k++) {
         c->as_bound = next_as_bound(c->as_bound, f[k]);
@@ -2021,6 +2031,54 @@ int mpt_get_framebuffer(MptContext* c, int kind, float* dst, int dst_is_device) 
     size_t bytes = 3 * (size_t)c->n_slots * sizeof(float);
     HIPCHK(hipMemcpyAsync(dst, src, bytes, dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return MPT_OK;
+}
+
+// The display step (DisplayViewSystem::display, Screenshoter::write_to_png): k_display on the
+// context's stream, ordered after the frames enqueued so far (every launch set ends joined into
+// the stream, as mpt_get_framebuffer relies on), reading the sums in place.  Only a host
+// destination (or a host second buffer, which must be copied before the call returns)
+// synchronises.
+int mpt_display(MptContext* c, const MptDisplaySettings* s, const float* second_rgb, int second_is_device, uint8_t* dst,
+                int dst_is_device) {
+    if (!c || !s || !dst) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (const char* e = mptdisp::display_settings_error(*s)) return fail(MPT_ERR_INVALID_ARGUMENT, e);
+    if (!c->rendered || !c->fb_color.p) return fail(MPT_ERR_INVALID_ARGUMENT, "display: no frame rendered");
+    if (s->view == MPT_VIEW_BLEND && !second_rgb)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "display: the blend view needs a second buffer");
+    const bool counts = mptdisp::view_reads_counts(s->view);
+    if (counts && !c->last_adaptive)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "display: the last frame had no adaptive-sampling buffers");
+    if (s->resolution_scaling > 1 && c->band_c > 1)
+        return fail(MPT_ERR_UNSUPPORTED, "display: resolution_scaling > 1 on a row partition (the block lives in other bands' rows)");
+    if (dst_is_device && ((uintptr_t)dst & 3u)) return fail(MPT_ERR_INVALID_ARGUMENT, "display: destination not 4-byte aligned");
+    HIPCHK(hipSetDevice(c->device));
+    int jr = join_waves(c);
+    if (jr != MPT_OK) return jr;
+    const size_t n = (size_t)c->n_slots;
+    const float* second = nullptr;
+    if (s->view == MPT_VIEW_BLEND) {
+        second = second_rgb;
+        if (!second_is_device) {
+            hipError_t e = c->disp_second.upload(second_rgb, 3 * n, c->stream);
+            if (e != hipSuccess) return alloc_fail(e, "display: second buffer");
+            HIPCHK(hipStreamSynchronize(c->stream));   // the caller's array is free once the call returns
+            second = c->disp_second.p;
+        }
+    }
+    uint32_t* out = (uint32_t*)dst;
+    if (!dst_is_device) {
+        hipError_t e = c->disp_out.alloc(std::max(n, (size_t)1));
+        if (e != hipSuccess) return alloc_fail(e, "display: staging buffer");
+        out = c->disp_out.p;
+    }
+    const float* src = s->view == MPT_VIEW_NORMALS ? c->fb_normal.p : s->view == MPT_VIEW_ALBEDO ? c->fb_albedo.p : c->fb_color.p;
+    const int rows = c->res_x > 0 ? c->n_slots / c->res_x : 0;
+    HIPCHK(launch_display(*s, src, second, c->as_conv.p, c->res_x, rows, out, c->stream));
+    if (!dst_is_device) {
+        HIPCHK(hipMemcpyAsync(dst, out, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     return MPT_OK;
 }
 

@@ -117,6 +117,7 @@ GPURenderer::GPURenderer(const std::vector<int>& devices) : m_devices(devices) {
     m_render_data.band_height = 1;
     m_render_data.band_index = 0;
     m_render_data.band_count = 1;
+    mpt_display_settings_default(&m_display_settings);
 }
 
 GPURenderer::~GPURenderer() {
@@ -344,6 +345,42 @@ void GPURenderer::unmap_buffers() {
     if (m_display.albedo) check(mpt_gather(m_ctxs.data(), n, 0, MPT_FB_ALBEDO, m_display.albedo, 1));
     if (m_display.normals) check(mpt_gather(m_ctxs.data(), n, 0, MPT_FB_NORMALS, m_display.normals, 1));
     m_mapped = false;
+}
+
+void GPURenderer::set_display_blend_buffer(const float* rgb, bool is_device, int sample_number) {
+    m_blend_rgb = rgb;
+    m_blend_is_device = is_device;
+    m_display_settings.sample_number_2 = sample_number;
+}
+
+void GPURenderer::display(uint8_t* dst, bool dst_is_device) {
+    // update_display_program_uniforms (DisplayViewSystem.cpp:198-329): render_settings.sample_number
+    // counts the samples rendered so far
+    DisplaySettings s = m_display_settings;
+    check(mpt_display_uniforms(&m_render_data.render_settings, m_display_view, m_was_last_frame_low_resolution ? 1 : 0, &s));
+    const bool blend = m_display_view == MPT_VIEW_BLEND;
+    if (m_ctxs.size() == 1) {
+        check(mpt_display(m_ctxs[0], &s, blend ? m_blend_rgb : nullptr, m_blend_is_device ? 1 : 0, dst, dst_is_device ? 1 : 0));
+        return;
+    }
+    // several contexts: each holds its bands' rows only (and none the whole low-resolution
+    // block), so the whole frame's source is gathered and displayed by the host's pixel functions
+    if (dst_is_device || (blend && m_blend_is_device))
+        throw std::runtime_error("GPURenderer::display: device buffers need a single context");
+    const size_t px = (size_t)m_width * m_height;
+    const bool counts = m_display_view == MPT_VIEW_PIXEL_CONVERGENCE_HEATMAP || m_display_view == MPT_VIEW_PIXEL_CONVERGED_MAP;
+    std::vector<float> src(counts ? px : px * 3);   // (the counts are 4 bytes per pixel too)
+    if (counts) get_aux_buffer(MPT_AUX_CONVERGED_SAMPLE_COUNT, src.data());
+    else get_framebuffer(m_display_view == MPT_VIEW_NORMALS ? MPT_FB_NORMALS : m_display_view == MPT_VIEW_ALBEDO ? MPT_FB_ALBEDO : MPT_FB_COLOR,
+                         src.data());
+    check(mpt_display_host(&s, src.data(), blend ? m_blend_rgb : nullptr, m_width, m_height, dst));
+}
+
+void GPURenderer::write_to_png(const char* filepath) {
+    synchronize_kernel();
+    std::vector<uint8_t> rgba((size_t)m_width * m_height * 4);
+    display(rgba.data(), false);
+    check(mpt_write_png(filepath, rgba.data(), m_width, m_height, 1));
 }
 
 void GPURenderer::copy_status_buffers() {

@@ -42,6 +42,9 @@ struct DisplayBuffers {
     float* normals = nullptr;    // denoiser normals AOV
 };
 
+// DisplaySettings (UI/DisplayView/DisplaySettings.h) with the display shaders' other uniforms
+using DisplaySettings = MptDisplaySettings;
+
 // ReSTIR DI across the row bands of several contexts of this process (mpt.h MptHaloExchange):
 // one host thread per context renders its band; at every exchange point each member
 // publishes its buffers, waits for the others, copies its halo rows from the owners (peer
@@ -147,6 +150,25 @@ public:
     void map_buffers_for_render();
     void unmap_buffers();
 
+    // The display step (DisplayViewSystem::display and the display shaders, mpt_display): the
+    // current view of everything rendered so far as RGBA8, W * H * 4 bytes, rows top to bottom.
+    // get_display_settings: DisplayViewSystem::get_display_settings (tonemapping, gamma, exposure,
+    // blend, white-furnace thresholds, heat-map stops); the per-view uniforms are derived from the
+    // render settings at every display (update_display_program_uniforms), the low-resolution
+    // scaling from was_last_frame_low_resolution().  A device destination is written by a kernel
+    // on the renderer's stream, without host synchronisation (one context only: the bands of
+    // several contexts are assembled on the host).
+    DisplaySettings& get_display_settings() { return m_display_settings; }
+    void set_display_view(int view) { m_display_view = view; }   // MPT_VIEW_* (DisplayViewType)
+    int get_display_view() const { return m_display_view; }
+    // MPT_VIEW_BLEND's second buffer (the reference blends in its denoiser's output; there is no
+    // denoiser here): W * H float3 sums, of the one context's device or the host, with their sample count
+    void set_display_blend_buffer(const float* rgb, bool is_device, int sample_number);
+    void display(uint8_t* dst, bool dst_is_device);
+    // Screenshoter::write_to_png (Screenshoter.cpp:129-166): synchronize_kernel, the display
+    // step, and an 8-bit RGBA PNG written bottom row first (stbi_flip_vertically_on_write(true))
+    void write_to_png(const char* filepath);
+
     MptRenderSettings& get_render_settings() { return m_render_data.render_settings; }
     MptWorldSettings& get_world_settings() { return m_render_data.world_settings; }
     MptKernelOptions& get_kernel_options() { return m_render_data.options; }   // KernelOptions.h macros, at run time
@@ -197,6 +219,10 @@ private:
     bool m_was_last_frame_low_resolution = false;
     std::string m_envmap_path;
     DisplayBuffers m_display;
+    DisplaySettings m_display_settings{};
+    int m_display_view = MPT_VIEW_DEFAULT;
+    const float* m_blend_rgb = nullptr;
+    bool m_blend_is_device = false;
     MptStatus m_status{};
     std::vector<MptMaterial> m_original_materials, m_current_materials;
     std::vector<MptFrame> m_pending;        // samples enqueued by the launches of this render()

@@ -21,7 +21,8 @@ from . import abi
 from . import scene
 from ._build import LIB_PATH
 
-__all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows"]
+__all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
+           "display_host", "write_png"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -32,6 +33,7 @@ SYMBOLS = [
     "mpt_set_halo_native", "mpt_halo_plan", "mpt_set_pipeline",
     "mpt_bake_lut", "mpt_png_unfilter", "mpt_device_info", "mpt_gather", "mpt_comm_unique_id", "mpt_comm_init",
     "mpt_comm_gather", "mpt_jpeg_decode", "mpt_hdr_decode",
+    "mpt_display_settings_default", "mpt_display_uniforms", "mpt_display", "mpt_display_host", "mpt_write_png",
 ]
 
 
@@ -101,6 +103,11 @@ def lib() -> C.CDLL:
     L.mpt_comm_gather.argtypes = [vp, i32, C.c_int, vp, C.c_int]
     L.mpt_jpeg_decode.argtypes = [vp, C.c_int64, i32, vp, C.c_int64, vp, vp, vp]
     L.mpt_hdr_decode.argtypes = [vp, C.c_int64, i32, vp, C.c_int64, vp, vp]
+    L.mpt_display_settings_default.argtypes = [C.POINTER(abi.DisplaySettings)]
+    L.mpt_display_uniforms.argtypes = [C.POINTER(abi.RenderSettings), i32, i32, C.POINTER(abi.DisplaySettings)]
+    L.mpt_display.argtypes = [vp, C.POINTER(abi.DisplaySettings), vp, C.c_int, vp, C.c_int]
+    L.mpt_display_host.argtypes = [C.POINTER(abi.DisplaySettings), vp, vp, i32, i32, vp]
+    L.mpt_write_png.argtypes = [C.c_char_p, vp, i32, i32, i32]
     _lib = L
     return L
 
@@ -115,9 +122,14 @@ def _p(a):
 
 
 def abi_sizes():
-    out = np.zeros(7, np.int32)
-    _check(lib().mpt_abi_sizes(_p(out), 7))
-    return dict(zip(["Material", "RenderSettings", "WorldSettings", "Camera", "Frame", "Scene", "Stats"], out.tolist()))
+    out = np.zeros(8, np.int32)
+    _check(lib().mpt_abi_sizes(_p(out), 8))
+    sizes = dict(zip(["Material", "RenderSettings", "WorldSettings", "Camera", "Frame", "Scene", "Stats",
+                      "DisplaySettings"], out.tolist()))
+    if sizes["DisplaySettings"] != C.sizeof(abi.DisplaySettings):
+        raise MptError(abi.ERR_INVALID_ARGUMENT, f"MptDisplaySettings is {sizes['DisplaySettings']} bytes in libmpt.so, "
+                       f"{C.sizeof(abi.DisplaySettings)} in mpt.abi")
+    return sizes
 
 
 def device_info(device=0):
@@ -192,6 +204,48 @@ def build_envmap(rgba):
     _check(lib().mpt_build_envmap_cdf(_p(rgba), w, h, _p(cdf), _p(cs)))
     return {"rgba": rgba, "probas": probas, "alias": alias, "width": w, "height": h, "sum": float(s[0]),
             "cdf": cdf, "cdf_sum": float(cs[0])}
+
+
+def display_settings(render_settings=None, view=abi.VIEW_DEFAULT, low_resolution=False, base=None):
+    """abi.DisplaySettings for `view`: mpt_display_settings_default (or a copy of `base`), then,
+    given the reference's render settings (sample_number = samples rendered so far), the per-view
+    uniforms of mpt_display_uniforms."""
+    s = abi.DisplaySettings()
+    if base is not None:
+        C.memmove(C.byref(s), C.byref(base), C.sizeof(s))
+    else:
+        _check(lib().mpt_display_settings_default(C.byref(s)))
+    s.view = view
+    if render_settings is not None:
+        _check(lib().mpt_display_uniforms(C.byref(render_settings), view, int(bool(low_resolution)), C.byref(s)))
+    return s
+
+
+def display_host(settings, src, src2=None):
+    """mpt_display_host: the display view of host arrays, no GPU.  src: float32 [H, W, 3] (int32
+    [H, W] for the heat map and the converged map), src2: the blend view's second buffer ->
+    uint8 [H, W, 4]."""
+    counts = settings.view in (abi.VIEW_PIXEL_CONVERGENCE_HEATMAP, abi.VIEW_PIXEL_CONVERGED_MAP)
+    src = np.ascontiguousarray(src, np.int32 if counts else np.float32)
+    if src.ndim != (2 if counts else 3) or (not counts and src.shape[2] != 3):
+        raise ValueError(f"display_host: source of shape {src.shape}")
+    h, w = src.shape[:2]
+    if src2 is not None:
+        src2 = np.ascontiguousarray(src2, np.float32)
+        if src2.shape != (h, w, 3):
+            raise ValueError(f"display_host: second buffer of shape {src2.shape}")
+    out = np.zeros((h, w, 4), np.uint8)
+    _check(lib().mpt_display_host(C.byref(settings), _p(src), _p(src2), w, h, _p(out)))
+    return out
+
+
+def write_png(path, rgba8, flip_y=False):
+    """mpt_write_png: uint8 [H, W, 4] -> an 8-bit RGBA PNG (flip_y: last row first, as the
+    reference's screenshots are written)."""
+    img = np.ascontiguousarray(rgba8, np.uint8)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError(f"write_png: image of shape {img.shape}")
+    _check(lib().mpt_write_png(os.fsencode(path), _p(img), img.shape[1], img.shape[0], int(bool(flip_y))))
 
 
 class GPURenderer:
@@ -314,6 +368,44 @@ class GPURenderer:
 
     def framebuffer_to_device(self, kind, dev_ptr: int):
         _check(lib().mpt_get_framebuffer(self.h, kind, C.c_void_p(dev_ptr), 1))
+
+    # --- display views / screenshots (DisplayViewSystem, Screenshoter) ---------------------
+    def display_settings(self, view=abi.VIEW_DEFAULT, low_resolution=False, base=None):
+        """The view's settings from the last frame's render settings, as
+        update_display_program_uniforms derives them after that frame: the reference's
+        sample_number counts the samples rendered, i.e. the last MptFrame's sample_number + 1."""
+        if self.frame is None:
+            raise MptError(abi.ERR_INVALID_ARGUMENT, "display: no frame rendered")
+        rs = abi.RenderSettings.from_buffer_copy(self.frame.render_settings)
+        rs.sample_number += 1
+        return display_settings(rs, view, low_resolution, base)
+
+    def _display(self, view, settings, second, second_is_device, low_resolution, dst, dst_is_device):
+        s = settings if settings is not None else self.display_settings(view, low_resolution)
+        _check(lib().mpt_display(self.h, C.byref(s), second, int(second_is_device), dst, int(dst_is_device)))
+
+    def display(self, view=abi.VIEW_DEFAULT, settings=None, second=None, low_resolution=False):
+        """mpt_display to the host: the partition's rows as uint8 [rows, W, 4] (RGBA).  settings:
+        an abi.DisplaySettings (its own view counts), else derived from the last frame
+        (display_settings).  second (VIEW_BLEND): float32 [rows, W, 3] host array, or a device
+        pointer (int) to such a buffer."""
+        out = np.zeros((self.rows(), self.frame.res_x, 4), np.uint8)
+        if isinstance(second, (int, np.integer)):
+            sec, dev = C.c_void_p(int(second)), True
+        else:
+            second = None if second is None else np.ascontiguousarray(second, np.float32)
+            if second is not None and second.size != 3 * out.shape[0] * out.shape[1]:
+                raise ValueError(f"display: second buffer of shape {second.shape}")
+            sec, dev = _p(second), False
+        self._display(view, settings, sec, dev, low_resolution, _p(out), False)
+        return out
+
+    def display_to_device(self, dev_ptr: int, view=abi.VIEW_DEFAULT, settings=None, second_dev_ptr: int | None = None,
+                          low_resolution=False):
+        """mpt_display into device memory (rows * W * 4 bytes at dev_ptr): enqueued on the
+        context's stream after the frames rendered so far, no host synchronisation."""
+        sec = C.c_void_p(int(second_dev_ptr)) if second_dev_ptr else None
+        self._display(view, settings, sec, True, low_resolution, C.c_void_p(int(dev_ptr)), True)
 
     # --- one process per GPU (RCCL, mpt_comm_*) ----------------------------------------
     def comm_init(self, nranks: int, rank: int, uid: bytes):

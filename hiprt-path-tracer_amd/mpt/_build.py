@@ -19,7 +19,7 @@ INCLUDE = ROOT.parent / "include"
 LIB_PATH = PKG_DIR / "libmpt.so"
 OBJ_DIR = CSRC / "build"
 
-SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp"]
+SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp", "display.hip"]
 # mpt_part.hip is compiled once per part (-DMPT_TU_PART=k): the shading and ReSTIR DI kernel
 # instantiations, so that they compile in parallel with the rest
 PARTS = [1, 2, 3, 4, 5, 6, 7]
@@ -78,26 +78,35 @@ def build(force: bool = False, verbose: bool = True, defines=(), out: Path | Non
 HOST_DIR = ROOT / "host"
 HOST_TEST = HOST_DIR / "gpurenderer_parity"
 HOST_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "gpurenderer_parity.cpp"]
+# the display step's driver (tests/test_display_host_cpp.py): the same mirror, another main
+DISPLAY_TEST = HOST_DIR / "display_views"
+DISPLAY_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "display_views.cpp"]
 
 
-def build_host_test(verbose: bool = True) -> Path:
-    """The C++ GPURenderer mirror (host/) linked with libmpt into the test driver of
-    tests/test_host_cpp.py (plain g++: the host side is ordinary C++ over the C ABI)."""
-    lib = build(verbose=verbose)
-    deps = HOST_SOURCES + sorted(HOST_DIR.glob("*.h")) + [lib]
-    if HOST_TEST.exists() and all(p.stat().st_mtime <= HOST_TEST.stat().st_mtime for p in deps):
-        return HOST_TEST
-    # the driver also calls the HIP runtime API itself (hipMalloc'd display buffers)
+def _build_driver(exe: Path, sources, lib: Path, verbose: bool) -> Path:
+    deps = list(sources) + sorted(HOST_DIR.glob("*.h")) + [lib]
+    if exe.exists() and all(p.stat().st_mtime <= exe.stat().st_mtime for p in deps):
+        return exe
+    # the drivers also call the HIP runtime API themselves (hipMalloc'd display buffers)
     cmd = ["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", f"-I{INCLUDE}", f"-I{HOST_DIR}", "-I/opt/rocm/include",
-           *map(str, HOST_SOURCES), f"-L{PKG_DIR}", "-lmpt", "-L/opt/rocm/lib", "-lamdhip64",
+           *map(str, sources), f"-L{PKG_DIR}", "-lmpt", "-L/opt/rocm/lib", "-lamdhip64",
            "-Wl,-rpath,$ORIGIN/../mpt", "-Wl,-rpath,/opt/rocm/lib",
-           "-Wl,-rpath-link,/opt/rocm/lib", "-o", str(HOST_TEST)]
+           "-Wl,-rpath-link,/opt/rocm/lib", "-o", str(exe)]
     if verbose:
         print("[mpt build]", " ".join(cmd), file=sys.stderr)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     if r.returncode != 0:
         raise RuntimeError("host test build failed:\n" + r.stdout.decode(errors="replace"))
-    return HOST_TEST
+    return exe
+
+
+def build_host_test(verbose: bool = True) -> Path:
+    """The C++ GPURenderer mirror (host/) linked with libmpt into the test drivers of
+    tests/test_host_cpp.py and tests/test_display_host_cpp.py (plain g++: the host side is
+    ordinary C++ over the C ABI)."""
+    lib = build(verbose=verbose)
+    _build_driver(DISPLAY_TEST, DISPLAY_SOURCES, lib, verbose)
+    return _build_driver(HOST_TEST, HOST_SOURCES, lib, verbose)
 
 
 if __name__ == "__main__":

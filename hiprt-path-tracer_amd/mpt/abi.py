@@ -414,11 +414,36 @@ class HaloOp(C.Structure):
     _fields_ = [("peer", C.c_int32), ("recv", C.c_int32), ("buffer", C.c_int32), ("row_lo", C.c_int32),
                 ("row_hi", C.c_int32)]
 
-ABI_SIZES = {"Material": 332, "RenderSettings": 304, "WorldSettings": 200, "Camera": 196}
+# Display views (mpt.h MPT_VIEW_*, numbered as DisplayViewType, DisplayViewEnum.h)
+VIEW_DEFAULT, VIEW_BLEND, VIEW_NORMALS, VIEW_ALBEDO = 0, 1, 2, 4
+VIEW_PIXEL_CONVERGENCE_HEATMAP, VIEW_PIXEL_CONVERGED_MAP, VIEW_WHITE_FURNACE_THRESHOLD = 6, 7, 8
+VIEWS = (VIEW_DEFAULT, VIEW_BLEND, VIEW_NORMALS, VIEW_ALBEDO, VIEW_PIXEL_CONVERGENCE_HEATMAP,
+         VIEW_PIXEL_CONVERGED_MAP, VIEW_WHITE_FURNACE_THRESHOLD)
+DISPLAY_MAX_STOPS = 16
+
+
+class DisplaySettings(C.Structure):
+    """MptDisplaySettings: the display shaders' uniforms (DisplaySettings.h and what
+    DisplayViewSystem::update_display_program_uniforms derives)."""
+    _fields_ = [("view", i32), ("sample_number", i32), ("sample_number_2", i32), ("resolution_scaling", i32),
+                ("do_tonemapping", i32), ("gamma", f32), ("exposure", f32), ("blend_factor", f32),
+                ("use_low_threshold", i32), ("use_high_threshold", i32), ("min_val", f32), ("max_val", f32),
+                ("threshold_val", f32), ("nb_stops", i32), ("color_stops", Color * DISPLAY_MAX_STOPS)]
+
+    @classmethod
+    def default(cls):
+        """mpt_display_settings_default (DisplaySettings.h; the heat map's stops, DisplayViewSystem.cpp:294)."""
+        s = cls(VIEW_DEFAULT, 1, 1, 1, 1, 2.2, 1.8, 1.0, 0, 1, 1.0, 1.0, 1.0, 3)
+        s.color_stops[0], s.color_stops[1], s.color_stops[2] = Color(0, 0, 1), Color(0, 1, 0), Color(1, 0, 0)
+        return s
+
+
+ABI_SIZES = {"Material": 332, "RenderSettings": 304, "WorldSettings": 200, "Camera": 196, "DisplaySettings": 248}
 
 
 def check_sizes():
     got = {"Material": C.sizeof(Material), "RenderSettings": C.sizeof(RenderSettings),
-           "WorldSettings": C.sizeof(WorldSettings), "Camera": C.sizeof(Camera)}
+           "WorldSettings": C.sizeof(WorldSettings), "Camera": C.sizeof(Camera),
+           "DisplaySettings": C.sizeof(DisplaySettings)}
     assert got == ABI_SIZES, got
     return got

@@ -27,6 +27,8 @@
  *                                    (GPURenderer.h:193-197, RenderData.h:32-36)
  *   mpt_trace_closest / mpt_trace_any <- hiprtGeomTraversalClosest/AnyHit as called by
  *                                    trace_ray / evaluate_shadow_ray (Device/includes/Intersect.h:114-286)
+ *   mpt_display / mpt_write_png   <- DisplayViewSystem::display + the display shaders (src/Shaders) and
+ *                                    Screenshoter::write_to_png (Screenshoter.cpp:129-166)
  *   mpt_bake_lut                  <- GPUBaker::bake_* (Renderer/Baker/GPUBaker.cpp:35-97) and the
  *                                    Device/kernels/Baking/ headers kernels
  *
@@ -542,7 +544,7 @@ typedef int (*MptHaloExchangeFn)(void* user, MptHaloExchange* x);
 const char* mpt_last_error(void);
 int mpt_version(void);
 /* sizes of the mirrored structs as compiled into the library (ABI check): MptMaterial,
- * MptRenderSettings, MptWorldSettings, MptCamera, MptFrame, MptScene, MptStats */
+ * MptRenderSettings, MptWorldSettings, MptCamera, MptFrame, MptScene, MptStats, MptDisplaySettings */
 int mpt_abi_sizes(int32_t* out_sizes, int n);
 /* The HIP device's marketing name, its gfx architecture string and compute-unit count (the
  * bench line's device identity); any output may be NULL. */
@@ -708,6 +710,80 @@ int mpt_jpeg_decode(const uint8_t* data, int64_t size, int32_t req_comp, uint8_t
  * three channels, alpha 1.  out = NULL: dimensions only.  Rows top to bottom (the caller flips). */
 int mpt_hdr_decode(const uint8_t* data, int64_t size, int32_t req_comp, float* out, int64_t out_cap,
                    int32_t* out_w, int32_t* out_h);
+
+/* ------------------------------------------------------------------------- */
+/* Display views and screenshots: the sums as 8-bit RGBA                      */
+/* ------------------------------------------------------------------------- */
+/* The reference turns its buffers into an image with seven display shaders (src/Shaders/ *.frag),
+ * which DisplayViewSystem::display runs once per displayed frame and Screenshoter::write_to_png
+ * (Screenshoter.cpp:129-166) runs as compute shaders writing RGBA8.  Here the same arithmetic, in
+ * fp32 and in the order written, is one kernel on the context's stream (csrc/display.hip) and one
+ * host loop (the same pixel functions, csrc/display.h); the two agree bit for bit.
+ * Views, numbered as DisplayViewType (DisplayViewEnum.h; the two denoised-AOV views, which the
+ * reference has disabled, are not offered): */
+#define MPT_VIEW_DEFAULT 0                    /* default_display.frag: 'pixels' / sample_number, tonemapped */
+#define MPT_VIEW_BLEND 1                      /* blend_2_display.frag (DENOISED_BLEND): 'pixels' and a second RGB sum */
+#define MPT_VIEW_NORMALS 2                    /* normal_display.frag: the normals AOV */
+#define MPT_VIEW_ALBEDO 4                     /* albedo_display.frag: the albedo AOV */
+#define MPT_VIEW_PIXEL_CONVERGENCE_HEATMAP 6  /* heatmap_int.frag: pixel_converged_sample_count */
+#define MPT_VIEW_PIXEL_CONVERGED_MAP 7        /* boolmap_int.frag: pixel_converged_sample_count */
+#define MPT_VIEW_WHITE_FURNACE_THRESHOLD 8    /* white_furnace_threshold.frag: 'pixels' */
+#define MPT_DISPLAY_MAX_STOPS 16
+
+/* The shaders' uniforms (DisplaySettings.h and what update_display_program_uniforms derives,
+ * DisplayViewSystem.cpp:198-329).  Every component v of a shader's output becomes the byte
+ * trunc(v * 255) (uvec4(v * 255)), saturated to [0, 255], NaN -> 0 (GLSL leaves those undefined). */
+typedef struct MptDisplaySettings {
+    int32_t view;               /* MPT_VIEW_* */
+    int32_t sample_number;      /* u_sample_number / u_sample_number_1 */
+    int32_t sample_number_2;    /* BLEND: u_sample_number_2, the second buffer's sample count */
+    int32_t resolution_scaling; /* u_resolution_scaling s >= 1: output (x, y) reads source (x / s, y / s) */
+    int32_t do_tonemapping;     /* 1: 1 - exp(-c * exposure), then pow(., 1 / gamma) */
+    float gamma;
+    float exposure;
+    float blend_factor;         /* BLEND: 0 = the first buffer, 1 = the second */
+    int32_t use_low_threshold;  /* WHITE_FURNACE_THRESHOLD: green below 0.49 */
+    int32_t use_high_threshold; /* WHITE_FURNACE_THRESHOLD: red above 0.51 */
+    float min_val;              /* heat map: the count of the first colour stop ... */
+    float max_val;              /* ... and of the last; min_val <= max_val */
+    float threshold_val;        /* converged map: white where 0 <= count < threshold_val */
+    int32_t nb_stops;           /* heat map: 1..MPT_DISPLAY_MAX_STOPS */
+    MptColor color_stops[MPT_DISPLAY_MAX_STOPS];
+} MptDisplaySettings;
+
+/* DisplaySettings.h's defaults (tonemapping on, gamma 2.2, exposure 1.8, blend 1, low threshold
+ * off, high on), view DEFAULT, one sample, no scaling, the heat map's blue / green / red stops
+ * (DisplayViewSystem.cpp:294) over [1, 1].  Host only. */
+int mpt_display_settings_default(MptDisplaySettings* out);
+/* What update_display_program_uniforms (DisplayViewSystem.cpp:203-324) derives from the render
+ * settings of the last frame for `view`, written into inout (its other fields stay):
+ * sample_number = max(1, render_settings->sample_number) -- the reference's count of samples
+ * rendered so far, i.e. the last MptFrame's sample_number + 1; resolution_scaling =
+ * render_low_resolution_scaling when low_resolution_displayed, else 1; min_val =
+ * adaptive_sampling_min_samples under enable_adaptive_sampling, else 1; max_val = threshold_val =
+ * max(sample_number, min_val).  Host only. */
+int mpt_display_uniforms(const MptRenderSettings* render_settings, int32_t view, int32_t low_resolution_displayed,
+                         MptDisplaySettings* inout);
+/* RGBA8 (bytes r, g, b, a) of the partition's rows, in the compact row order of
+ * mpt_get_framebuffer: one kernel on the context's stream, after the frames enqueued so far,
+ * reading the context's sums in place.  dst: rows * res_x * 4 bytes, device (asynchronous: no
+ * host synchronisation) or host memory (synchronous).  second_rgb (BLEND only): 3 floats per
+ * pixel in the partition's layout, device or host memory (a host array is copied before the call
+ * returns).  resolution_scaling > 1 shows the top-left ceil(W / s) x ceil(H / s) block a
+ * low-resolution frame renders, scaled up; a context of a row partition (band_count > 1) holds
+ * only its own rows of that block: MPT_ERR_UNSUPPORTED.  The heat map and the converged map need
+ * the last frame to have had the adaptive-sampling buffers (adaptive sampling or the stop-noise
+ * threshold, while accumulating). */
+int mpt_display(MptContext* ctx, const MptDisplaySettings* settings, const float* second_rgb, int second_is_device,
+                uint8_t* dst_rgba8, int dst_is_device);
+/* The same pixel functions on host arrays, no GPU: src is width * height float3 (int32 counts
+ * for the heat map and the converged map), src2 the second float3 buffer of BLEND (else NULL). */
+int mpt_display_host(const MptDisplaySettings* settings, const void* src, const float* src2, int32_t width,
+                     int32_t height, uint8_t* dst_rgba8);
+/* 8-bit RGBA PNG of width x height pixels (rows top to bottom), stored (uncompressed) deflate
+ * blocks.  flip_y = 1 writes the last row first, as stbi_flip_vertically_on_write(true) does for
+ * the reference's screenshots (Screenshoter.cpp:162-163).  Host only. */
+int mpt_write_png(const char* path, const uint8_t* rgba8, int32_t width, int32_t height, int32_t flip_y);
 
 #ifdef __cplusplus
 }
