@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "bvh8.h"
+#include "denoise.h"
 #include "display.h"
 #include "mpt.h"
 #include "mpt_internal.h"
@@ -315,6 +316,10 @@ struct MptContext {
     bool rendered = false, last_adaptive = false;
     DBuf<uint32_t> disp_out;
     DBuf<float> disp_second;
+    // mpt_denoise / mpt_denoise_device: the working planes (denoise.hip), the kept result, the
+    // sample count it was made at (0: nothing denoised since the last resize)
+    DBuf<float> den_scratch, den_out;
+    int den_samples = 0;
 };
 
 namespace {
@@ -560,6 +565,8 @@ int ensure_paths(MptContext* c, int rx, int ry, int bh, int bi, int bc) {
     release_batch(c);                       // sized for the previous partition
     c->res_x = c->res_y = c->n_slots = 0;   // no partition until the group below is complete
     c->rendered = false;
+    c->den_samples = 0;
+    release_all(c->den_scratch, c->den_out);
     c->as_bound = 1 << 30;
     const size_t N = (size_t)std::max(n, 1);
     hipStream_t st = c->stream;
@@ -1319,6 +1326,11 @@ int mpt_resize(MptContext* c, int32_t w, int32_t h) {
     if ((int64_t)w * h > MPT_MAX_WAVEFRONT_PATHS) return fail(MPT_ERR_UNSUPPORTED, "more than MPT_MAX_WAVEFRONT_PATHS pixels");
     int r = ensure_paths(c, w, h, c->band_h, c->band_i, c->band_c);
     if (r != MPT_OK) return r;
+    if (c->den_scratch.p || c->den_out.p) {   // the denoiser's planes go with every resize
+        HIPCHK(drain(c));
+        release_all(c->den_scratch, c->den_out);
+    }
+    c->den_samples = 0;
     return ensure_batch(c, 1, false);
 }
 
@@ -2080,6 +2092,70 @@ int mpt_display(MptContext* c, const MptDisplaySettings* s, const float* second_
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return MPT_OK;
+}
+
+// The denoiser (RenderWindow::denoise with an a-trous filter in OIDN's place, denoise.hip): 1 +
+// iterations kernels on the context's stream, ordered after the frames enqueued so far like
+// mpt_display; the working planes are the context's, allocated when their size changes.
+static int denoise_run(MptContext* c, const MptDenoiseSettings& s, const float* color, const float* albedo,
+                       const float* normals, int w, int h, float* dst) {
+    const size_t want = mpt::denoise_scratch_floats((int64_t)std::max(w, 1) * std::max(h, 1));
+    if (c->den_scratch.n != want) {
+        HIPCHK(drain(c));   // kernels of an earlier call may still read the planes
+        hipError_t e = c->den_scratch.alloc(want);
+        if (e != hipSuccess) return alloc_fail(e, "denoise: working planes");
+    }
+    HIPCHK(launch_denoise(s, color, albedo, normals, w, h, c->den_scratch.p, dst, c->stream));
+    return MPT_OK;
+}
+
+int mpt_denoise(MptContext* c, const MptDenoiseSettings* s, float* dst, int dst_is_device) {
+    if (!c || !s) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (const char* e = mptden::denoise_settings_error(*s)) return fail(MPT_ERR_INVALID_ARGUMENT, e);
+    if (!c->rendered || !c->fb_color.p) return fail(MPT_ERR_INVALID_ARGUMENT, "denoise: no frame rendered");
+    if (c->band_c > 1)
+        return fail(MPT_ERR_UNSUPPORTED, "denoise: a row partition holds only its own rows of the stencil "
+                                         "(mpt_gather the colour, albedo and normals planes, then mpt_denoise_device)");
+    HIPCHK(hipSetDevice(c->device));
+    int jr = join_waves(c);
+    if (jr != MPT_OK) return jr;
+    const size_t n = (size_t)c->n_slots;
+    if (c->den_out.n != 3 * std::max(n, (size_t)1)) {
+        HIPCHK(drain(c));
+        c->den_samples = 0;
+        hipError_t e = c->den_out.alloc(3 * std::max(n, (size_t)1));
+        if (e != hipSuccess) return alloc_fail(e, "denoise: result buffer");
+    }
+    const int rows = c->res_x > 0 ? c->n_slots / c->res_x : 0;
+    int r = denoise_run(c, *s, c->fb_color.p, c->fb_albedo.p, c->fb_normal.p, c->res_x, rows, c->den_out.p);
+    if (r != MPT_OK) return r;
+    c->den_samples = s->sample_number;
+    if (dst) {
+        HIPCHK(hipMemcpyAsync(dst, c->den_out.p, 3 * n * sizeof(float), dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                              c->stream));
+        if (!dst_is_device) HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return MPT_OK;
+}
+
+int mpt_denoised_buffer(MptContext* c, const float** dev, int32_t* sample_number) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (c->den_samples < 1 || !c->den_out.p) return fail(MPT_ERR_INVALID_ARGUMENT, "denoise: nothing denoised since the last resize");
+    if (dev) *dev = c->den_out.p;
+    if (sample_number) *sample_number = c->den_samples;
+    return MPT_OK;
+}
+
+int mpt_denoise_device(MptContext* c, const MptDenoiseSettings* s, const float* color, const float* albedo, const float* normals,
+                       int32_t w, int32_t h, float* dst) {
+    if (!c || !s || !color || !albedo || !normals || !dst) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (const char* e = mptden::denoise_settings_error(*s)) return fail(MPT_ERR_INVALID_ARGUMENT, e);
+    if (w <= 0 || h <= 0) return fail(MPT_ERR_INVALID_ARGUMENT, "denoise: bad size");
+    if ((int64_t)w * h > MPT_MAX_WAVEFRONT_PATHS) return fail(MPT_ERR_UNSUPPORTED, "denoise: more than MPT_MAX_WAVEFRONT_PATHS pixels");
+    HIPCHK(hipSetDevice(c->device));
+    int jr = join_waves(c);
+    if (jr != MPT_OK) return jr;
+    return denoise_run(c, *s, color, albedo, normals, w, h, dst);
 }
 
 // ---------------------------------------------------------------------------------------

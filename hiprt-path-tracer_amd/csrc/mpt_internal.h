@@ -403,6 +403,11 @@ hipError_t launch_env_rich(const DevScene& S, float4* out, hipStream_t st);
 // display.hip: rows x W pixels of the partition as RGBA8 words (src / src2: 3 floats per slot, cnt: int32 per slot)
 hipError_t launch_display(const MptDisplaySettings& S, const float* src, const float* src2, const int32_t* cnt, int W,
                           int rows, uint32_t* dst, hipStream_t st);
+// denoise.hip: prepare + the a-trous iterations of W x H float3 planes into dst (W * H float3);
+// scratch: denoise_scratch_floats(W * H) floats, 16-byte aligned
+size_t denoise_scratch_floats(int64_t pixels);
+hipError_t launch_denoise(const MptDenoiseSettings& S, const float* color, const float* albedo, const float* normals,
+                          int W, int H, float* scratch, float* dst, hipStream_t st);
 hipError_t launch_trace_raw(const DevScene& S, const float4* o, const float4* d, int n, bool any, float4* out_hit,
                             uint8_t* out_occ, int32_t* fetch_ctr, uint32_t* spill, int grid, hipStream_t st);
 

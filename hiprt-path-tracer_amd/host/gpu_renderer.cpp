@@ -118,6 +118,7 @@ GPURenderer::GPURenderer(const std::vector<int>& devices) : m_devices(devices) {
     m_render_data.band_index = 0;
     m_render_data.band_count = 1;
     mpt_display_settings_default(&m_display_settings);
+    mpt_denoise_settings_default(&m_denoise_settings);
 }
 
 GPURenderer::~GPURenderer() {
@@ -374,6 +375,29 @@ void GPURenderer::display(uint8_t* dst, bool dst_is_device) {
     else get_framebuffer(m_display_view == MPT_VIEW_NORMALS ? MPT_FB_NORMALS : m_display_view == MPT_VIEW_ALBEDO ? MPT_FB_ALBEDO : MPT_FB_COLOR,
                          src.data());
     check(mpt_display_host(&s, src.data(), blend ? m_blend_rgb : nullptr, m_width, m_height, dst));
+}
+
+void GPURenderer::denoise() {
+    if (m_ctxs.size() != 1) throw std::runtime_error("GPURenderer::denoise: needs a single context (gather the bands first)");
+    DenoiseSettings s = m_denoise_settings;
+    s.sample_number = m_render_data.render_settings.sample_number > 1 ? m_render_data.render_settings.sample_number : 1;
+    check(mpt_denoise(m_ctxs[0], &s, nullptr, 1));
+}
+
+const float* GPURenderer::get_denoised_framebuffer(int* sample_number) {
+    if (m_ctxs.size() != 1) throw std::runtime_error("GPURenderer::get_denoised_framebuffer: needs a single context");
+    const float* dev = nullptr;
+    int32_t n = 0;
+    check(mpt_denoised_buffer(m_ctxs[0], &dev, &n));
+    if (sample_number) *sample_number = n;
+    return dev;
+}
+
+void GPURenderer::set_display_blend_to_denoised() {
+    int n = 0;
+    const float* dev = get_denoised_framebuffer(&n);
+    set_display_blend_buffer(dev, true, n);
+    set_display_view(MPT_VIEW_BLEND);
 }
 
 void GPURenderer::write_to_png(const char* filepath) {

@@ -44,6 +44,8 @@ struct DisplayBuffers {
 
 // DisplaySettings (UI/DisplayView/DisplaySettings.h) with the display shaders' other uniforms
 using DisplaySettings = MptDisplaySettings;
+// the settings of the a-trous denoiser that stands in OIDN's place (mpt_denoise)
+using DenoiseSettings = MptDenoiseSettings;
 
 // ReSTIR DI across the row bands of several contexts of this process (mpt.h MptHaloExchange):
 // one host thread per context renders its band; at every exchange point each member
@@ -161,13 +163,29 @@ public:
     DisplaySettings& get_display_settings() { return m_display_settings; }
     void set_display_view(int view) { m_display_view = view; }   // MPT_VIEW_* (DisplayViewType)
     int get_display_view() const { return m_display_view; }
-    // MPT_VIEW_BLEND's second buffer (the reference blends in its denoiser's output; there is no
-    // denoiser here): W * H float3 sums, of the one context's device or the host, with their sample count
+    // MPT_VIEW_BLEND's second buffer (the reference blends in its denoiser's output; see denoise()
+    // and set_display_blend_to_denoised() below): W * H float3 sums, of the one context's device or
+    // the host, with their sample count
     void set_display_blend_buffer(const float* rgb, bool is_device, int sample_number);
     void display(uint8_t* dst, bool dst_is_device);
     // Screenshoter::write_to_png (Screenshoter.cpp:129-166): synchronize_kernel, the display
     // step, and an 8-bit RGBA PNG written bottom row first (stbi_flip_vertically_on_write(true))
     void write_to_png(const char* filepath);
+
+    // The denoiser (RenderWindow::denoise -> OpenImageDenoiser::denoise; here mpt_denoise's a-trous
+    // filter, no OIDN parity): denoises everything rendered so far on the renderer's stream, without
+    // host synchronisation; sample_number is taken from the render settings at every call.  The
+    // gating of RenderWindow::denoise (sample skip, denoise only when done) is UI state and the
+    // caller's.  One context only: the bands of several contexts are gathered first (mpt_gather,
+    // mpt_denoise_device).
+    DenoiseSettings& get_denoise_settings() { return m_denoise_settings; }
+    void denoise();
+    // OpenImageDenoiser::get_denoised_framebuffer with last_denoised_sample_count: the device
+    // buffer of the last denoise() (W * H float3 sums)
+    const float* get_denoised_framebuffer(int* sample_number = nullptr);
+    // display() and write_to_png() show MPT_VIEW_BLEND of the sums and the last denoise()'s result
+    // (blend factor: get_display_settings().blend_factor, 1 = the denoised image)
+    void set_display_blend_to_denoised();
 
     MptRenderSettings& get_render_settings() { return m_render_data.render_settings; }
     MptWorldSettings& get_world_settings() { return m_render_data.world_settings; }
@@ -223,6 +241,7 @@ private:
     int m_display_view = MPT_VIEW_DEFAULT;
     const float* m_blend_rgb = nullptr;
     bool m_blend_is_device = false;
+    DenoiseSettings m_denoise_settings{};
     MptStatus m_status{};
     std::vector<MptMaterial> m_original_materials, m_current_materials;
     std::vector<MptFrame> m_pending;        // samples enqueued by the launches of this render()

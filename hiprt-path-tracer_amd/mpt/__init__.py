@@ -22,7 +22,7 @@ from . import scene
 from ._build import LIB_PATH
 
 __all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
-           "display_host", "write_png"]
+           "display_host", "write_png", "denoise_host"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -34,6 +34,7 @@ SYMBOLS = [
     "mpt_bake_lut", "mpt_png_unfilter", "mpt_device_info", "mpt_gather", "mpt_comm_unique_id", "mpt_comm_init",
     "mpt_comm_gather", "mpt_jpeg_decode", "mpt_hdr_decode",
     "mpt_display_settings_default", "mpt_display_uniforms", "mpt_display", "mpt_display_host", "mpt_write_png",
+    "mpt_denoise_settings_default", "mpt_denoise", "mpt_denoised_buffer", "mpt_denoise_device", "mpt_denoise_host",
 ]
 
 
@@ -108,6 +109,11 @@ def lib() -> C.CDLL:
     L.mpt_display.argtypes = [vp, C.POINTER(abi.DisplaySettings), vp, C.c_int, vp, C.c_int]
     L.mpt_display_host.argtypes = [C.POINTER(abi.DisplaySettings), vp, vp, i32, i32, vp]
     L.mpt_write_png.argtypes = [C.c_char_p, vp, i32, i32, i32]
+    L.mpt_denoise_settings_default.argtypes = [C.POINTER(abi.DenoiseSettings)]
+    L.mpt_denoise.argtypes = [vp, C.POINTER(abi.DenoiseSettings), vp, C.c_int]
+    L.mpt_denoised_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(i32)]
+    L.mpt_denoise_device.argtypes = [vp, C.POINTER(abi.DenoiseSettings), vp, vp, vp, i32, i32, vp]
+    L.mpt_denoise_host.argtypes = [C.POINTER(abi.DenoiseSettings), vp, vp, vp, i32, i32, vp]
     _lib = L
     return L
 
@@ -246,6 +252,19 @@ def write_png(path, rgba8, flip_y=False):
     if img.ndim != 3 or img.shape[2] != 4:
         raise ValueError(f"write_png: image of shape {img.shape}")
     _check(lib().mpt_write_png(os.fsencode(path), _p(img), img.shape[1], img.shape[0], int(bool(flip_y))))
+
+
+def denoise_host(settings, color, albedo, normals):
+    """mpt_denoise_host: the a-trous denoiser on host arrays, no GPU.  color (sums over
+    settings.sample_number samples), albedo, normals: float32 [H, W, 3] -> float32 [H, W, 3], sums
+    in the units of `color`."""
+    color, albedo, normals = (np.ascontiguousarray(a, np.float32) for a in (color, albedo, normals))
+    if color.ndim != 3 or color.shape[2] != 3 or albedo.shape != color.shape or normals.shape != color.shape:
+        raise ValueError(f"denoise_host: planes of shapes {color.shape}, {albedo.shape}, {normals.shape}")
+    out = np.zeros_like(color)
+    _check(lib().mpt_denoise_host(C.byref(settings), _p(color), _p(albedo), _p(normals), color.shape[1], color.shape[0],
+                                  _p(out)))
+    return out
 
 
 class GPURenderer:
@@ -406,6 +425,55 @@ class GPURenderer:
         context's stream after the frames rendered so far, no host synchronisation."""
         sec = C.c_void_p(int(second_dev_ptr)) if second_dev_ptr else None
         self._display(view, settings, sec, True, low_resolution, C.c_void_p(int(dev_ptr)), True)
+
+    # --- denoiser (RenderWindow::denoise; an a-trous filter in OIDN's place) ----------------
+    def denoise_settings(self, base=None):
+        """abi.DenoiseSettings (the defaults, or a copy of `base`) with sample_number = the samples
+        rendered so far, i.e. the last MptFrame's sample_number + 1, as display_settings() counts."""
+        if self.frame is None:
+            raise MptError(abi.ERR_INVALID_ARGUMENT, "denoise: no frame rendered")
+        s = abi.DenoiseSettings.default()
+        if base is not None:
+            C.memmove(C.byref(s), C.byref(base), C.sizeof(s))
+        s.sample_number = self.frame.render_settings.sample_number + 1
+        return s
+
+    def denoise(self, settings=None):
+        """mpt_denoise to the host: the denoised sums, float32 [rows, W, 3]; the result also stays
+        on the device (denoised()).  settings=None: denoise_settings()."""
+        s = settings if settings is not None else self.denoise_settings()
+        if self.frame is None:
+            raise MptError(abi.ERR_INVALID_ARGUMENT, "denoise: no frame rendered")
+        out = np.zeros((self.rows(), self.frame.res_x, 3), np.float32)
+        _check(lib().mpt_denoise(self.h, C.byref(s), _p(out), 0))
+        return out
+
+    def denoise_to_device(self, dev_ptr: int | None = None, settings=None):
+        """mpt_denoise on the context's stream, no host synchronisation; dev_ptr (rows * W float3
+        of device memory) also receives the kept result, None keeps it only."""
+        s = settings if settings is not None else self.denoise_settings()
+        _check(lib().mpt_denoise(self.h, C.byref(s), C.c_void_p(int(dev_ptr)) if dev_ptr else None, 1))
+
+    def denoised(self):
+        """mpt_denoised_buffer: (device pointer of the kept result, the sample_number it was made at)."""
+        p, n = C.c_void_p(), C.c_int32()
+        _check(lib().mpt_denoised_buffer(self.h, C.byref(p), C.byref(n)))
+        return int(p.value), int(n.value)
+
+    def denoise_device(self, settings, color_ptr: int, albedo_ptr: int, normals_ptr: int, w: int, h: int, dst_ptr: int):
+        """mpt_denoise_device: caller-owned device planes of w x h float3 (e.g. gathered from a row
+        partition), on the context's stream; asynchronous."""
+        _check(lib().mpt_denoise_device(self.h, C.byref(settings), C.c_void_p(int(color_ptr)), C.c_void_p(int(albedo_ptr)),
+                                        C.c_void_p(int(normals_ptr)), w, h, C.c_void_p(int(dst_ptr))))
+
+    def display_denoised(self, blend=1.0, settings=None):
+        """The BLEND view of the sums and the kept denoised result (blend 0: the sums, 1: the
+        denoised image) -> uint8 [rows, W, 4].  settings: an abi.DisplaySettings to start from."""
+        ptr, n = self.denoised()
+        s = self.display_settings(abi.VIEW_BLEND, base=settings)
+        s.sample_number_2 = n
+        s.blend_factor = blend
+        return self.display(settings=s, second=ptr)
 
     # --- one process per GPU (RCCL, mpt_comm_*) ----------------------------------------
     def comm_init(self, nranks: int, rank: int, uid: bytes):

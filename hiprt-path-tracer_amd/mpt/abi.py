@@ -438,6 +438,19 @@ class DisplaySettings(C.Structure):
         return s
 
 
+class DenoiseSettings(C.Structure):
+    """MptDenoiseSettings: the a-trous denoiser's settings (mpt.h)."""
+    _fields_ = [("sample_number", i32), ("iterations", i32), ("use_albedo", i32), ("use_normals", i32),
+                ("sigma_color", f32), ("sigma_albedo", f32), ("normal_power_log2", i32)]
+
+    @classmethod
+    def default(cls):
+        """mpt_denoise_settings_default."""
+        return cls(1, 5, 1, 1, 4.0, 0.1, 6)
+
+
+DENOISE_MAX_ITERATIONS = 8
+
 ABI_SIZES = {"Material": 332, "RenderSettings": 304, "WorldSettings": 200, "Camera": 196, "DisplaySettings": 248}
 
 

@@ -29,6 +29,9 @@
  *                                    trace_ray / evaluate_shadow_ray (Device/includes/Intersect.h:114-286)
  *   mpt_display / mpt_write_png   <- DisplayViewSystem::display + the display shaders (src/Shaders) and
  *                                    Screenshoter::write_to_png (Screenshoter.cpp:129-166)
+ *   mpt_denoise / mpt_denoised_buffer <- RenderWindow::denoise (RenderWindow.cpp:881-972) and
+ *                                    OpenImageDenoiser::denoise / get_denoised_framebuffer, with an
+ *                                    a-trous filter in OIDN's place (no parity claimed)
  *   mpt_bake_lut                  <- GPUBaker::bake_* (Renderer/Baker/GPUBaker.cpp:35-97) and the
  *                                    Device/kernels/Baking/ headers kernels
  *
@@ -784,6 +787,61 @@ int mpt_display_host(const MptDisplaySettings* settings, const void* src, const 
  * blocks.  flip_y = 1 writes the last row first, as stbi_flip_vertically_on_write(true) does for
  * the reference's screenshots (Screenshoter.cpp:162-163).  Host only. */
 int mpt_write_png(const char* path, const uint8_t* rgba8, int32_t width, int32_t height, int32_t flip_y);
+
+/* ------------------------------------------------------------------------- */
+/* Denoiser: an edge-avoiding a-trous filter guided by the AOVs               */
+/* ------------------------------------------------------------------------- */
+/* The reference denoises with OIDN (RenderWindow::denoise, RenderWindow.cpp:881-972;
+ * OpenImageDenoiser::denoise / get_denoised_framebuffer) and blends the result in with the BLEND
+ * view.  OIDN is not available here; in its place stands a self-contained, deterministic filter
+ * that claims no parity with it: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on
+ * albedo-demodulated radiance, its edge stopping taken from the normals AOV, the albedo AOV and
+ * the colour itself (the definition: DESIGN.md §2).  Inputs: three planes of float3 per pixel --
+ * the colour sums over sample_number samples (MPT_FB_COLOR) and the albedo and normals averages
+ * (MPT_FB_ALBEDO, MPT_FB_NORMALS; 0 where the camera ray missed).  Output: float3 sums over
+ * sample_number samples, i.e. in the units of the input; the BLEND view takes it as its second
+ * buffer with sample_number_2 = sample_number.  All arithmetic is fp32 in a fixed order; the
+ * kernels (csrc/denoise.hip) and the host loop share the pixel functions (csrc/denoise.h) and
+ * agree bit for bit. */
+#define MPT_DENOISE_MAX_ITERATIONS 8
+typedef struct MptDenoiseSettings {
+    int32_t sample_number;      /* samples in the colour sums, >= 1 */
+    int32_t iterations;         /* 1..MPT_DENOISE_MAX_ITERATIONS; iteration i has its taps 1 << i pixels apart */
+    int32_t use_albedo;         /* demodulate by max(albedo, 0.01) and stop at albedo edges */
+    int32_t use_normals;        /* stop at normal edges: weight max(0, n_p . n_q) ^ (2 ^ normal_power_log2) */
+    float sigma_color;          /* colour edge stopping, halved at every iteration; finite, > 0 */
+    float sigma_albedo;         /* albedo edge stopping; finite, > 0 */
+    int32_t normal_power_log2;  /* 0..10 */
+} MptDenoiseSettings;
+
+/* One sample, 5 iterations, albedo and normals on, sigma_color 4, sigma_albedo 0.1,
+ * normal_power_log2 6.  Host only. */
+int mpt_denoise_settings_default(MptDenoiseSettings* out);
+/* Denoises the context's own colour sums with its AOV buffers: 1 + iterations kernels on the
+ * context's stream, after the frames enqueued so far, reading the buffers in place.  The result
+ * stays in a context-owned device buffer (mpt_denoised_buffer) and is also copied to
+ * dst_rgb_or_NULL (rows * res_x float3): a device destination is asynchronous (no host
+ * synchronisation), a host destination makes the call synchronous.  The working planes (40 B per
+ * pixel) and the result live in the context, allocated at the first call and dropped by
+ * mpt_resize.  MPT_ERR_INVALID_ARGUMENT before any frame was rendered; MPT_ERR_UNSUPPORTED on a
+ * context of a row partition (band_count > 1), whose stencil would need other bands' rows:
+ * mpt_gather the three planes and use mpt_denoise_device. */
+int mpt_denoise(MptContext* ctx, const MptDenoiseSettings* settings, float* dst_rgb_or_NULL, int dst_is_device);
+/* The result mpt_denoise kept (device pointer, valid until the next mpt_denoise, mpt_resize or a
+ * frame of another partition) and the sample_number it was made at: the reference's
+ * get_denoised_framebuffer and last_denoised_sample_count.  The pointer is what mpt_display takes
+ * as a device second buffer, with sample_number_2 = *sample_number.  Either output may be NULL.
+ * MPT_ERR_INVALID_ARGUMENT when nothing was denoised since the last resize. */
+int mpt_denoised_buffer(MptContext* ctx, const float** dev, int32_t* sample_number);
+/* The same kernels on caller-owned device planes of width x height float3 (on the context's
+ * device), with the context's stream and working planes; dst (device, width * height float3) may
+ * be one of the inputs.  Asynchronous.  The multi-GPU route: mpt_gather the three planes to the
+ * root's device, then denoise there. */
+int mpt_denoise_device(MptContext* ctx, const MptDenoiseSettings* settings, const float* color, const float* albedo,
+                       const float* normals, int32_t width, int32_t height, float* dst);
+/* The same pixel functions in a host loop, no GPU: host arrays of width * height float3. */
+int mpt_denoise_host(const MptDenoiseSettings* settings, const float* color, const float* albedo, const float* normals,
+                     int32_t width, int32_t height, float* dst);
 
 #ifdef __cplusplus
 }
