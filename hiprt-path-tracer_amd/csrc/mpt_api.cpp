@@ -306,6 +306,11 @@ struct MptContext {
     // frame restarts it, every frame with the adaptive buffers adds at most one sample; unknown
     // (large) until a reset frame has been launched
     int as_bound = 1 << 30;
+    // a converged count may be set since the last reset (note_conv_set): by a stop-noise frame, or
+    // by an adaptive frame whose bound had passed that frame's minimum.  While it is set, as_bound
+    // at most an adaptive frame's minimum no longer means that no pixel has converged
+    // (restir_gate_static); cleared with the converged counts (a reset frame, a new partition)
+    bool as_conv_set = false;
     // the last batch reset the adaptive buffers in its k_accumulate (which an overlapped next batch
     // would run beside): the next ReSTIR DI batch does not overlap it
     bool as_reset_pending = false;
@@ -568,6 +573,7 @@ int ensure_paths(MptContext* c, int rx, int ry, int bh, int bi, int bc) {
     c->den_samples = 0;
     release_all(c->den_scratch, c->den_out);
     c->as_bound = 1 << 30;
+    c->as_conv_set = false;   // (as_conv is set to -1 below)
     const size_t N = (size_t)std::max(n, 1);
     hipStream_t st = c->stream;
     Allocs A;
@@ -1523,6 +1529,17 @@ static int next_as_bound(int b, const MptFrame& f) {
     if (is_reset(f)) b = 0;
     return b < (1 << 30) ? b + 1 : b;
 }
+// MptContext::as_conv_set after frame f, `bound` being as_bound before it: the frame's gate
+// (AdaptiveSampling.h:30-104) can set pixel_converged_sample_count under enable_adaptive_sampling
+// only at a count above the frame's minimum, in the stop-noise-only branch from sample number 2
+// on whatever the count; a reset frame clears the counts first (CameraRays.h:90-91)
+static bool note_conv_set(bool set, int bound, const MptFrame& f) {
+    if (!has_adaptive(f)) return set;
+    const MptRenderSettings& rs = f.render_settings;
+    if (is_reset(f)) { set = false; bound = 0; }
+    if (rs.enable_adaptive_sampling) return set || bound > rs.adaptive_sampling_min_samples;
+    return set || (rs.enable_pixel_stop_noise_threshold && rs.sample_number > 1);
+}
 // The trace-ahead stream of a single-stream wavefront (frame_bounces): streamx[1], its spill area
 // and events, on first use
 // (which = 1: streamx[0] with its own events, for the first half of an overlapped batch, whose
@@ -1698,8 +1715,10 @@ static int launch_batch(MptContext* c, const MptFrame* f, int batch) {
     {
         const MptRenderSettings& rs = f->render_settings;
         P.spec_as = batch > 1 && (rs.stop_pixel_noise_threshold > 0.0f || rs.enable_adaptive_sampling) && rs.accumulate;
-        // a pixel converges only at a gate with its count above the minimum, so while the bound on
-        // the counts is at most the minimum no pixel has converged and none is left out
+        // a pixel converges at this run's gate only with its count above the minimum, so while the
+        // bound on the counts is at most the minimum none is left out.  (A count set earlier under
+        // other settings, as_conv_set, is then traced for nothing: k_accumulate's gate refuses the
+        // sample all the same, and ReSTIR DI does not batch such frames, restir_gate_static.)
         P.spec_skip = P.spec_as && rs.enable_adaptive_sampling && c->as_bound > rs.adaptive_sampling_min_samples;
     }
     if (restir_part) {   // frame_begin maintains the band and the previous frame's halo rows
@@ -1868,6 +1887,7 @@ static int launch_batch(MptContext* c, const MptFrame* f, int batch) {
     c->last_adaptive = has_adaptive(f[batch - 1]);
     c->as_reset_pending = false;
     for (int k = 0; k < batch; k++) {
+        c->as_conv_set = note_conv_set(c->as_conv_set, c->as_bound, f[k]);
         c->as_bound = next_as_bound(c->as_bound, f[k]);
         c->as_reset_pending |= batch > 1 && has_adaptive(f[k]) && is_reset(f[k]);
     }
@@ -1949,9 +1969,18 @@ static bool batchable(const MptContext* c, const MptFrame& a, const MptFrame& b)
 // noise test (pixel_sample_count > adaptive_sampling_min_samples): it then refuses exactly the
 // pixels that had converged before the batch (sticky) and passes the others, and the converged
 // counts do not change.  So frame i + k may join a run starting at frame i when neither is a reset
-// frame (a reset clears the converged counts the passes read) and the host's bound on
-// pixel_sample_count before it, as_bound + k, is at most the minimum.  The stop-noise threshold
-// alone never refuses a sample and the passes do not read its counts: always static.
+// frame (a reset clears the converged counts the passes read), the host's bound on
+// pixel_sample_count before it, as_bound + k, is at most the minimum, and no converged count can
+// have been set since the last reset (MptContext::as_conv_set).  The bound argument holds only
+// with the last condition: it speaks of counts set by this run's gate, but a count is sticky
+// under enable_adaptive_sampling whoever set it (AdaptiveSampling.h:45-48) -- the stop-noise-only
+// branch from 2 samples on (AdaptiveSampling.h:79-101), or adaptive frames with a smaller minimum
+// -- and a sequential render gives such a pixel no camera ray and skips it as a centre pixel of
+// the reuse passes, while a batch called static (spec_skip off: as_bound is at most the minimum)
+// would run it through them and change its reservoirs and those of the neighbours that reuse
+// them.  So once a count may be set the adaptive frames run one by one until the next reset.
+// The stop-noise threshold alone never refuses a sample and the passes do not read its counts:
+// always static.
 // A run may also start with a reset frame: the passes read the converged counts -- which the
 // batch's k_accumulate resets only at its end -- only at sample numbers of at least the minimum
 // (restir_spatial_neighbor), so the run's sample numbers stay below it.
@@ -1962,7 +1991,7 @@ static bool restir_gate_static(const MptContext* c, const MptFrame* run, int k) 
     if (is_reset(run[k])) return false;
     const int mn = rs.adaptive_sampling_min_samples;
     if (is_reset(a)) return k <= mn && a.render_settings.sample_number < mn && run[k].render_settings.sample_number < mn;
-    return (int64_t)c->as_bound + k <= (int64_t)mn;
+    return !c->as_conv_set && (int64_t)c->as_bound + k <= (int64_t)mn;
 }
 
 // The overlapped ReSTIR DI wavefronts of the call joined into the context's stream: everything
