@@ -130,6 +130,8 @@ void build_bvh8(const float* vertices, const int32_t* indices, int32_t num_trian
                 float pad_in, int sah_depth) {
     out.nodes.clear();
     out.tris.clear();
+    out.level_begin.clear();
+    out.node_box.clear();
     if (num_triangles <= 0) return;
     max_leaf = std::max(1, std::min(4, max_leaf));
     Builder b;
@@ -253,6 +255,7 @@ void build_bvh8(const float* vertices, const int32_t* indices, int32_t num_trian
     while (qi < queue.size()) {
         Item it = queue[qi++];
         max_depth = std::max(max_depth, it.depth);
+        if ((int)out.level_begin.size() < it.depth) out.level_begin.push_back(it.n8);   // breadth first: depths ascend
         // gather up to 8 children
         std::vector<int> ch;
         const N2& r2 = b.nodes[it.n2];
@@ -359,7 +362,10 @@ void build_bvh8(const float* vertices, const int32_t* indices, int32_t num_trian
             }
         }
         out.nodes[it.n8] = nd;
+        out.node_box.resize(6 * out.nodes.size());
+        for (int a = 0; a < 3; a++) { out.node_box[6 * (size_t)it.n8 + a] = nb.lo[a]; out.node_box[6 * (size_t)it.n8 + 3 + a] = nb.hi[a]; }
     }
+    out.level_begin.push_back((int32_t)out.nodes.size());
     out.depth = max_depth;
 }
 

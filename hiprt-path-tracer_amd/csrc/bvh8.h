@@ -41,6 +41,10 @@ struct BVH8 {
     std::vector<TriRec> tris;
     int depth = 0;
     float sah_cost = 0.0f;
+    // refits (refit.h): the first node index of each breadth-first level, then the node count
+    // (depth + 1 entries), and each node's exact, unquantised box (6 floats: lo, hi)
+    std::vector<int32_t> level_begin;
+    std::vector<float> node_box;
 };
 
 // Builds the BVH8 over indexed triangles.  max_leaf: triangles per leaf child (<= 4).

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +20,7 @@
 #include "display.h"
 #include "mpt.h"
 #include "mpt_internal.h"
+#include "refit.h"
 
 using namespace mpt;
 
@@ -167,6 +169,15 @@ struct MptContext {
     std::vector<int32_t> h_idx;           // host copies for rebuilding the light BVH on material edits
     std::vector<float> h_pos;
     float box_pad = 0.0f;
+    // mpt_update_vertices (refit.hip): the exact node boxes of both trees (6 floats per node) and
+    // the records' padded boxes (scratch); the area sums of the builders' node boxes; whether the
+    // host copies bvh.tris, bvh_light.tris and h_pos still hold the positions before an update
+    // (refresh_mirrors); which vertices the triangles use (the pad is taken over these)
+    DBuf<float> nbox, nbox_light, tbox;
+    double area0 = 0.0, area0_light = 0.0;
+    bool mirrors_stale = false;
+    std::vector<uint8_t> h_vert_used;
+    int refit_host_loop = 0;              // test hook (MPT_REFIT_HOST): the refit by the host loop of refit.h
     int light_bvh = 1;                    // MPT_LIGHT_BVH at mpt_create: 0 = one closest-hit traversal per light-hit query
     bool light_bvh_ok = false;            // the light BVH matches the materials (else: the exact closest-hit path)
     int light_bvh_max_stack = 1 << 30;    // test hook (MPT_LIGHT_BVH_MAX_STACK): a lower traversal-stack limit
@@ -595,6 +606,23 @@ int ensure_paths(MptContext* c, int rx, int ry, int bh, int bi, int bc) {
     return MPT_OK;
 }
 
+// The host copies of the triangle records and of the positions brought up to the device's, after
+// mpt_update_vertices refitted those on the GPU: before a material edit re-stamps and re-uploads
+// the records, or builds a changed light set (upload_alpha_flags, resolve_materials,
+// build_light_bvh_impl).  An update itself pays no host pass over the triangles.
+int refresh_mirrors(MptContext* c) {
+    if (!c->mirrors_stale) return MPT_OK;
+    hipStream_t st = c->stream;
+    if (c->tris.n != c->bvh.tris.size() || c->pos.n != c->h_pos.size()) return fail(MPT_ERR_HIP, "refresh_mirrors: sizes differ");
+    HIPCHK(hipMemcpyAsync(c->bvh.tris.data(), c->tris.p, c->tris.n * sizeof(TriRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_pos.data(), c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (c->tris_light.p && c->tris_light.n == c->bvh_light.tris.size())
+        HIPCHK(hipMemcpyAsync(c->bvh_light.tris.data(), c->tris_light.p, c->tris_light.n * sizeof(TriRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->mirrors_stale = false;
+    return MPT_OK;
+}
+
 // Alpha-test flag of every triangle record (TriRec::pad0): the filter function's test
 // (FilterFunction.h:19-48) can only reject a hit when alpha_opacity < 1 or the base
 // colour texture has a texel with alpha < 255; all other triangles skip it for free.
@@ -666,6 +694,7 @@ static int build_light_bvh_impl(MptContext* c, hipError_t& herr) {
                 c->h_light_prims.clear();
                 return MPT_OK;
             }
+            c->area0_light = node_box_area_sum(c->bvh_light.node_box.data(), c->bvh_light.nodes.size());
             for (TriRec& tr : c->bvh_light.tris) {   // subset index -> scene primitive
                 int32_t k;
                 std::memcpy(&k, &tr.prim_bits, 4);
@@ -1049,6 +1078,7 @@ int mpt_create(int device, void* hip_stream, MptContext** out) {
     if (const char* e = std::getenv("MPT_LIGHT_BVH")) c->light_bvh = std::atoi(e);
     if (const char* e = std::getenv("MPT_OVERLAP")) c->overlap = std::atoi(e);
     if (const char* e = std::getenv("MPT_LIGHT_BVH_MAX_STACK")) c->light_bvh_max_stack = std::atoi(e);
+    if (const char* e = std::getenv("MPT_REFIT_HOST")) c->refit_host_loop = std::atoi(e);
     int r = create_context(c, device, hip_stream);
     if (r != MPT_OK) {
         const std::string msg = g_err;
@@ -1115,19 +1145,12 @@ int mpt_upload_scene(MptContext* c, const MptScene* s) {
         if (s->emissive_triangle_indices[i] < 0 || s->emissive_triangle_indices[i] >= s->num_triangles)
             return fail(MPT_ERR_INVALID_ARGUMENT, "emissive triangle index out of range");
     HIPCHK(hipSetDevice(c->device));
-    // triangles per leaf child: 3 (MPT_BVH_LEAF, 1..4, development A/B)
-    int max_leaf = 3;
-    if (const char* e = std::getenv("MPT_BVH_LEAF")) max_leaf = std::max(1, std::min(4, std::atoi(e)));
-    // per level: at most one node group and one postponed triangle group on the stack; a
-    // tree too deep for the traversal stack is rebuilt with balanced splits from a smaller
-    // depth on (test hook MPT_BVH_MAX_STACK: a lower limit)
-    int stack_cap = MAX_STACK;
-    if (const char* e = std::getenv("MPT_BVH_MAX_STACK")) stack_cap = std::max(4, std::min(MAX_STACK, std::atoi(e)));
-    for (int sah_depth = 40;; sah_depth = sah_depth * 2 / 3) {
-        build_bvh8(s->vertices, s->triangle_indices, s->num_triangles, c->bvh, max_leaf, -1.0f, sah_depth);
-        if (2 * c->bvh.depth + 2 <= stack_cap || sah_depth == 0) break;
-    }
+    const int stack_cap = build_scene_bvh8(s->vertices, s->triangle_indices, s->num_triangles, c->bvh, MAX_STACK);
     c->box_pad = scene_box_pad(s->vertices, s->num_triangles, s->triangle_indices);
+    c->area0 = node_box_area_sum(c->bvh.node_box.data(), c->bvh.nodes.size());
+    c->mirrors_stale = false;
+    c->h_vert_used.assign((size_t)s->num_vertices, 0);
+    for (size_t k = 0; k < 3 * (size_t)s->num_triangles; k++) c->h_vert_used[s->triangle_indices[k]] = 1;
     c->h_idx.assign(s->triangle_indices, s->triangle_indices + 3 * (size_t)s->num_triangles);
     c->h_pos.assign(s->vertices, s->vertices + 3 * (size_t)s->num_vertices);
     c->h_light_prims.clear();
@@ -1199,6 +1222,10 @@ int mpt_update_materials(MptContext* c, const MptMaterial* m, int32_t count) {
     if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
     if (count != (int32_t)c->h_mats.size()) return fail(MPT_ERR_INVALID_ARGUMENT, "material count differs from the scene's");
     HIPCHK(hipSetDevice(c->device));
+    {
+        const int rm = refresh_mirrors(c);
+        if (rm != MPT_OK) return rm;
+    }
     c->h_mats.assign(m, m + count);
     HIPCHK(c->mats.upload(c->h_mats.data(), c->h_mats.size(), c->stream));
     std::vector<int32_t> prio(count);
@@ -1210,6 +1237,127 @@ int mpt_update_materials(MptContext* c, const MptMaterial* m, int32_t count) {
     rr = build_light_bvh(c);
     if (rr != MPT_OK) return rr;
     return resolve_materials(c);
+}
+
+namespace {
+
+// The device side of mpt_update_vertices: uploads, the refit of both trees, the tables derived
+// from the positions.  Any HIP error is returned; the caller then drops the scene.
+hipError_t update_vertices_device(MptContext* c, const float* v, const float* nrm, float pad) {
+#define UV(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+    hipStream_t st = c->stream;
+    UV(drain(c));
+    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
+    UV(hipMemcpyAsync(c->pos.p, v, c->pos.n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (nrm) UV(hipMemcpyAsync(c->nrm.p, nrm, c->nrm.n * sizeof(float), hipMemcpyHostToDevice, st));
+    UV(c->nbox.alloc(6 * c->nodes.n));
+    if (light) UV(c->nbox_light.alloc(6 * c->nodes_light.n));
+    if (c->refit_host_loop) {
+        // (the host copies' w lanes are always current; their positions are rewritten here)
+        std::vector<float> hb;
+        refit_host(c->bvh, c->h_idx.data(), v, pad, hb);
+        UV(hipMemcpyAsync(c->nodes.p, c->bvh.nodes.data(), c->nodes.n * sizeof(Node8), hipMemcpyHostToDevice, st));
+        UV(hipMemcpyAsync(c->tris.p, c->bvh.tris.data(), c->tris.n * sizeof(TriRec), hipMemcpyHostToDevice, st));
+        UV(hipMemcpyAsync(c->nbox.p, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        UV(hipStreamSynchronize(st));
+        if (light) {
+            refit_host(c->bvh_light, c->h_idx.data(), v, pad, hb);
+            UV(hipMemcpyAsync(c->nodes_light.p, c->bvh_light.nodes.data(), c->nodes_light.n * sizeof(Node8), hipMemcpyHostToDevice, st));
+            UV(hipMemcpyAsync(c->tris_light.p, c->bvh_light.tris.data(), c->tris_light.n * sizeof(TriRec), hipMemcpyHostToDevice, st));
+            UV(hipMemcpyAsync(c->nbox_light.p, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice, st));
+            UV(hipStreamSynchronize(st));
+        }
+        c->h_pos.assign(v, v + c->pos.n);
+        c->mirrors_stale = false;
+    } else {
+        UV(c->tbox.alloc(6 * std::max(c->tris.n, light ? c->tris_light.n : (size_t)0)));
+        c->mirrors_stale = true;
+        UV(launch_refit_tris(c->tris.p, (int)c->tris.n, c->idx.p, c->pos.p, pad, c->tbox.p, st));
+        UV(launch_refit_levels(c->nodes.p, c->nbox.p, c->tbox.p, c->bvh.level_begin.data(), c->bvh.depth, st));
+        if (light) {   // the records hold scene primitive ids: the same path; the scene's pad
+            UV(launch_refit_tris(c->tris_light.p, (int)c->tris_light.n, c->idx.p, c->pos.p, pad, c->tbox.p, st));
+            UV(launch_refit_levels(c->nodes_light.p, c->nbox_light.p, c->tbox.p, c->bvh_light.level_begin.data(),
+                                   c->bvh_light.depth, st));
+        }
+    }
+    UV(launch_tri_attr(dev_scene(c), c->tri_attr.p, st));
+    // the emissive-triangle table holds positions (the materials' resolution comes out as it was)
+    UV(launch_resolve_materials(dev_scene(c), c->mats_res.p, c->mat_tex.p, (int)c->h_mats.size(), c->em_tab.p, st));
+    return hipStreamSynchronize(st);
+#undef UV
+}
+
+}  // namespace
+
+int mpt_update_vertices(MptContext* c, const float* vertices, const float* vertex_normals, int32_t num_vertices,
+                        MptRefitInfo* info) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!vertices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
+    // one pass: every coordinate finite, and scene_box_pad's maximum over the vertices in use
+    float m = 0.0f;
+    for (size_t i = 0; i < (size_t)num_vertices; i++) {
+        const float* p = vertices + 3 * i;
+        const float a0 = std::fabs(p[0]), a1 = std::fabs(p[1]), a2 = std::fabs(p[2]);
+        if (!(a0 <= FLT_MAX && a1 <= FLT_MAX && a2 <= FLT_MAX))   // (a NaN fails every comparison)
+            return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
+        if (c->h_vert_used[i]) m = std::max(m, std::max(a0, std::max(a1, a2)));
+    }
+    const float pad = std::ldexp(std::max(m, 1.0f), -20);
+    HIPCHK(hipSetDevice(c->device));
+    c->box_pad = pad;
+    hipError_t e = update_vertices_device(c, vertices, vertex_normals, pad);
+    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
+    std::vector<float> hb, hbl;
+    if (e == hipSuccess && info) {
+        hb.resize(c->nbox.n);
+        e = hipMemcpy(hb.data(), c->nbox.p, hb.size() * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && light) {
+            hbl.resize(c->nbox_light.n);
+            e = hipMemcpy(hbl.data(), c->nbox_light.p, hbl.size() * sizeof(float), hipMemcpyDeviceToHost);
+        }
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->has_scene = false;   // half updated: the caller uploads again
+        return fail(MPT_ERR_HIP, std::string("mpt_update_vertices: ") + hipGetErrorString(e));
+    }
+    if (info) {
+        MptRefitInfo r{};
+        r.nodes = (int32_t)c->nodes.n;
+        r.levels = c->bvh.depth;
+        r.area_ratio = (float)(node_box_area_sum(hb.data(), c->nodes.n) / c->area0);
+        if (light) {
+            r.light_nodes = (int32_t)c->nodes_light.n;
+            r.light_levels = c->bvh_light.depth;
+            r.light_area_ratio = (float)(node_box_area_sum(hbl.data(), c->nodes_light.n) / c->area0_light);
+        }
+        *info = r;
+    }
+    return MPT_OK;
+}
+
+int mpt_get_bvh(MptContext* c, int which, void* nodes, int64_t nodes_cap_bytes, void* tris, int64_t tris_cap_bytes,
+                int32_t* out_counts) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (which != 0 && which != 1) return fail(MPT_ERR_INVALID_ARGUMENT, "bvh: which must be 0 (scene) or 1 (light)");
+    if (nodes_cap_bytes < 0 || tris_cap_bytes < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "bvh: bad size");
+    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
+    const DBuf<Node8>& dn = which ? c->nodes_light : c->nodes;
+    const DBuf<TriRec>& dt = which ? c->tris_light : c->tris;
+    const size_t nn = which && !light ? 0 : dn.n, nt = which && !light ? 0 : dt.n;
+    const int levels = which ? (light ? c->bvh_light.depth : 0) : c->bvh.depth;
+    if (nodes_cap_bytes == 0 && tris_cap_bytes == 0) return copy_bvh_out(nullptr, nn, nullptr, nt, levels, nullptr, 0, nullptr, 0, out_counts);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(drain(c));
+    std::vector<Node8> hn(nn);
+    std::vector<TriRec> ht(nt);
+    if (nn) HIPCHK(hipMemcpy(hn.data(), dn.p, nn * sizeof(Node8), hipMemcpyDeviceToHost));
+    if (nt) HIPCHK(hipMemcpy(ht.data(), dt.p, nt * sizeof(TriRec), hipMemcpyDeviceToHost));
+    return copy_bvh_out(hn.data(), nn, ht.data(), nt, levels, nodes, nodes_cap_bytes, tris, tris_cap_bytes, out_counts);
 }
 
 int mpt_build_alias_table(const float* rgba, int32_t w, int32_t h, float* out_p, int32_t* out_a, float* out_sum) {

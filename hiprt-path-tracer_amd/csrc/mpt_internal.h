@@ -408,6 +408,17 @@ hipError_t launch_display(const MptDisplaySettings& S, const float* src, const f
 size_t denoise_scratch_floats(int64_t pixels);
 hipError_t launch_denoise(const MptDenoiseSettings& S, const float* color, const float* albedo, const float* normals,
                           int W, int H, float* scratch, float* dst, hipStream_t st);
+// refit.hip (refit.h): the records of a tree refitted to pos and their padded boxes into tbox (6
+// floats per record); then the node levels from the deepest to the root, one launch each
+// (level_begin: BVH8::level_begin, levels + 1 entries; node_box: 6 floats per node)
+hipError_t launch_refit_tris(TriRec* tris, int n, const int32_t* idx, const float* pos, float pad, float* tbox, hipStream_t st);
+hipError_t launch_refit_levels(Node8* nodes, float* node_box, const float* tbox, const int32_t* level_begin, int levels,
+                               hipStream_t st);
+// the scene BVH as mpt_upload_scene builds it (rebuilt shallower while too deep for stack_limit
+// entries); returns the stack limit in force (MPT_BVH_MAX_STACK)
+int build_scene_bvh8(const float* vertices, const int32_t* indices, int32_t num_triangles, BVH8& out, int stack_limit);
+int copy_bvh_out(const Node8* nodes, size_t n_nodes, const TriRec* tris, size_t n_tris, int levels, void* out_nodes,
+                 int64_t nodes_cap, void* out_tris, int64_t tris_cap, int32_t* out_counts);
 hipError_t launch_trace_raw(const DevScene& S, const float4* o, const float4* d, int n, bool any, float4* out_hit,
                             uint8_t* out_occ, int32_t* fetch_ctr, uint32_t* spill, int grid, hipStream_t st);
 

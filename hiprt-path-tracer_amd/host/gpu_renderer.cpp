@@ -136,6 +136,13 @@ void GPURenderer::update_materials(std::vector<MptMaterial>& materials) {
     m_current_materials = materials;
 }
 
+void GPURenderer::update_vertices(const float* vertices, const float* vertex_normals_or_null, int32_t num_vertices,
+                                  MptRefitInfo* info) {
+    for (size_t k = 0; k < m_ctxs.size(); k++)
+        check(mpt_update_vertices(m_ctxs[k], vertices, vertex_normals_or_null, num_vertices, k == 0 ? info : nullptr));
+    reset();   // samples, reservoirs and adaptive counters of the old geometry are stale
+}
+
 void GPURenderer::set_envmap(const float* rgba, int width, int height, const std::string& envmap_filepath) {
     // Image32Bit::compute_alias_table / compute_cdf (Image.cpp:553-659), restated in libmpt
     std::vector<float> prob((size_t)width * height), cdf((size_t)width * height);

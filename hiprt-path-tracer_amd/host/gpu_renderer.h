@@ -121,6 +121,12 @@ public:
     // update_materials (GPURenderer.h:228, .cpp:1196-1200): material edits of the front-end's
     // editor; re-uploaded and re-resolved (texture flags, material classes, light BVH)
     void update_materials(std::vector<MptMaterial>& materials);
+    // update_vertices (no counterpart in the reference, which rebuilds its geometry): new positions
+    // (3 floats per vertex of the scene, optionally new vertex normals) for the uploaded scene; every
+    // context refits its BVHs on its GPU (mpt_update_vertices).  The accumulation restarts: the next
+    // render carries need_to_reset, as after reset().  info (optional): the first context's report.
+    void update_vertices(const float* vertices, const float* vertex_normals_or_null, int32_t num_vertices,
+                         MptRefitInfo* info = nullptr);
     const std::vector<MptMaterial>& get_original_materials() const { return m_original_materials; }
     const std::vector<MptMaterial>& get_current_materials() const { return m_current_materials; }
 

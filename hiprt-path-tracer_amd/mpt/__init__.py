@@ -22,7 +22,7 @@ from . import scene
 from ._build import LIB_PATH
 
 __all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
-           "display_host", "write_png", "denoise_host"]
+           "display_host", "write_png", "denoise_host", "bvh_refit_host"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -35,6 +35,7 @@ SYMBOLS = [
     "mpt_comm_gather", "mpt_jpeg_decode", "mpt_hdr_decode",
     "mpt_display_settings_default", "mpt_display_uniforms", "mpt_display", "mpt_display_host", "mpt_write_png",
     "mpt_denoise_settings_default", "mpt_denoise", "mpt_denoised_buffer", "mpt_denoise_device", "mpt_denoise_host",
+    "mpt_update_vertices", "mpt_get_bvh", "mpt_bvh_refit_host",
 ]
 
 
@@ -114,6 +115,9 @@ def lib() -> C.CDLL:
     L.mpt_denoised_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(i32)]
     L.mpt_denoise_device.argtypes = [vp, C.POINTER(abi.DenoiseSettings), vp, vp, vp, i32, i32, vp]
     L.mpt_denoise_host.argtypes = [C.POINTER(abi.DenoiseSettings), vp, vp, vp, i32, i32, vp]
+    L.mpt_update_vertices.argtypes = [vp, vp, vp, i32, C.POINTER(abi.RefitInfo)]
+    L.mpt_get_bvh.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]
+    L.mpt_bvh_refit_host.argtypes = [vp, vp, i32, vp, i32, vp, C.c_int64, vp, C.c_int64, vp]
     _lib = L
     return L
 
@@ -267,6 +271,37 @@ def denoise_host(settings, color, albedo, normals):
     return out
 
 
+def _bvh_arrays(call):
+    """The two-step download of a BVH8: counts first, then the arrays."""
+    counts = np.zeros(3, np.int32)
+    _check(call(None, 0, None, 0, _p(counts)))
+    nodes = np.zeros(int(counts[0]), abi.NODE8_DTYPE)
+    tris = np.zeros(int(counts[1]), abi.TRIREC_DTYPE)
+    if counts[0] or counts[1]:
+        # (an empty array still needs a non-NULL pointer)
+        nb, tb = (a if a.size else np.zeros(1, a.dtype) for a in (nodes, tris))
+        _check(call(_p(nb), nodes.nbytes, _p(tb), tris.nbytes, _p(counts)))
+    return nodes, tris, int(counts[2])
+
+
+def bvh_refit_host(build_vertices, indices, new_vertices=None):
+    """mpt_bvh_refit_host, no GPU: the BVH8 built over build_vertices ([V, 3] float32) and indices
+    ([T, 3] int32) as an upload builds it, refitted to new_vertices by the host loop (None: the
+    builder's output).  Returns (nodes, tris, levels): structured arrays of abi.NODE8_DTYPE and
+    abi.TRIREC_DTYPE, the bytes GPURenderer.get_bvh(0) returns after update_vertices (the records'
+    flag lanes are 0 here)."""
+    bv = np.ascontiguousarray(build_vertices, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    nv = None
+    if new_vertices is not None:
+        nv = np.ascontiguousarray(new_vertices, np.float32).reshape(-1, 3)
+        if nv.shape != bv.shape:
+            raise ValueError(f"bvh_refit_host: {nv.shape[0]} new vertices for {bv.shape[0]}")
+    L = lib()
+    return _bvh_arrays(lambda n, nc, t, tc, cnt: L.mpt_bvh_refit_host(_p(bv), _p(nv), bv.shape[0], _p(idx), idx.shape[0],
+                                                                      n, nc, t, tc, cnt))
+
+
 class GPURenderer:
     """One renderer context on one GPU (GPURenderer.h:69)."""
 
@@ -289,6 +324,27 @@ class GPURenderer:
     def update_materials(self, materials):
         arr = (abi.Material * len(materials))(*materials)
         _check(lib().mpt_update_materials(self.h, C.cast(arr, C.c_void_p), len(materials)))
+
+    def update_vertices(self, vertices, normals=None, info=False):
+        """mpt_update_vertices: new positions ([V, 3] float32, the scene's vertex count) and
+        optionally new vertex normals for the uploaded scene; both BVHs are refitted on the GPU.
+        The next frame must carry need_to_reset (sample_number 0).  info=True returns the
+        abi.RefitInfo (a download of the node boxes), else None."""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        n = None
+        if normals is not None:
+            n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+            if n.shape != v.shape:
+                raise ValueError(f"update_vertices: {n.shape[0]} normals for {v.shape[0]} vertices")
+        ri = abi.RefitInfo() if info else None
+        _check(lib().mpt_update_vertices(self.h, _p(v), _p(n), v.shape[0], C.byref(ri) if info else None))
+        return ri
+
+    def get_bvh(self, which=0):
+        """mpt_get_bvh: (nodes, tris, levels) of the scene BVH (0) or the light-hit BVH (1) as the
+        kernels read them, structured arrays of abi.NODE8_DTYPE / abi.TRIREC_DTYPE."""
+        L = lib()
+        return _bvh_arrays(lambda n, nc, t, tc, cnt: L.mpt_get_bvh(self.h, which, n, nc, t, tc, cnt))
 
     def set_envmap(self, env):
         """GPURenderer::set_envmap (GPURenderer.cpp:1136-1174); env from build_envmap() or None."""

@@ -12,6 +12,8 @@ reference's in-class initialisers:
 """
 import ctypes as C
 
+import numpy as np
+
 c_bool = C.c_bool
 f32 = C.c_float
 i32 = C.c_int32
@@ -450,6 +452,20 @@ class DenoiseSettings(C.Structure):
 
 
 DENOISE_MAX_ITERATIONS = 8
+
+
+class RefitInfo(C.Structure):
+    """MptRefitInfo: what mpt_update_vertices reports (mpt.h)."""
+    _fields_ = [("nodes", i32), ("levels", i32), ("light_nodes", i32), ("light_levels", i32),
+                ("area_ratio", f32), ("light_area_ratio", f32)]
+
+
+# the BVH8 arrays of mpt_get_bvh / mpt_bvh_refit_host (csrc/bvh8.h): 80-byte nodes, 48-byte records
+NODE8_DTYPE = np.dtype([("p", "<f4", 3), ("e", "u1", 3), ("imask", "u1"), ("child_base", "<u4"), ("tri_base", "<u4"),
+                        ("meta", "u1", 8), ("qlo", "u1", (3, 8)), ("qhi", "u1", (3, 8))])
+TRIREC_DTYPE = np.dtype([("a", "<f4", 3), ("prim", "<i4"), ("e1", "<f4", 3), ("alpha_flag", "<u4"),
+                         ("e2", "<f4", 3), ("mat_class", "<u4")])
+assert NODE8_DTYPE.itemsize == 80 and TRIREC_DTYPE.itemsize == 48
 
 ABI_SIZES = {"Material": 332, "RenderSettings": 304, "WorldSettings": 200, "Camera": 196, "DisplaySettings": 248}
 

@@ -11,6 +11,8 @@
  *                                    (GPURenderer.h:220, GPURenderer.cpp:1041-1134) and
  *                                    HIPRTGeometry::build_bvh (HIPRTScene.h:60-87)
  *   mpt_update_materials          <- GPURenderer::update_materials (GPURenderer.h:228)
+ *   mpt_update_vertices           <- (no counterpart: the reference rebuilds its HIPRT geometry) moved
+ *                                    vertices with a GPU refit of both BVH8s
  *   mpt_set_envmap                <- GPURenderer::set_envmap (GPURenderer.h:222, .cpp:1136-1174)
  *   mpt_set_luts                  <- GPURenderer::setup_brdfs_data (GPURenderer.h:76, .cpp:88-175)
  *   mpt_resize                    <- GPURenderer::resize (GPURenderer.h:172)
@@ -557,6 +559,49 @@ int mpt_create(int device, void* hip_stream, MptContext** out_ctx);
 int mpt_destroy(MptContext* ctx);
 int mpt_upload_scene(MptContext* ctx, const MptScene* scene);
 int mpt_update_materials(MptContext* ctx, const MptMaterial* materials, int32_t count);
+
+/* Geometry updates (DESIGN.md §2 "Geometry updates").  What mpt_update_vertices reports; filling it
+ * costs a download of the exact node boxes, so it is only done when asked for.  area_ratio: the
+ * sum over the scene BVH's nodes of the surface area of the node's exact box after the refit,
+ * divided by the same sum at the last mpt_upload_scene (host, double, node order): 1 after an
+ * identity update; the host decides from it when a real rebuild (mpt_upload_scene) is due.
+ * light_*: the same of the light-hit BVH, against its last build (a material edit that changes
+ * the light set rebuilds it); zeros when no light BVH is in use. */
+typedef struct MptRefitInfo {
+    int32_t nodes, levels, light_nodes, light_levels;
+    float area_ratio, light_area_ratio;
+} MptRefitInfo;
+/* Replaces the vertex positions of the uploaded scene (and its vertex normals when given);
+ * topology, indices, materials, textures, has_vertex_normals and the emissive list stay.  The
+ * context's streams are drained, the arrays uploaded, and everything derived from positions is
+ * brought up to date on the GPU: the triangle records and node boxes of the scene BVH and of the
+ * light-hit BVH (a refit: the trees keep their topology and depth), the per-triangle attributes,
+ * the emissive-triangle table, the box pad.  Traversal results never depend on the BVH, so they
+ * equal those of a fresh upload of the new scene bit for bit; a tree refitted far from its build
+ * traverses more slowly (MptRefitInfo::area_ratio).
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT for NULL vertices, a vertex count
+ * that differs from the scene's or a non-finite coordinate -- a refused call changes nothing.
+ * MPT_ERR_HIP part-way through leaves the context without a scene: upload again.
+ * The caller's next frame must carry render_settings.need_to_reset (sample_number 0), as the
+ * reference's does when its scene changes: accumulated samples, ReSTIR DI reservoirs, G-buffers
+ * and adaptive-sampling counters of the old geometry are stale.  The library checks nothing
+ * about it. */
+int mpt_update_vertices(MptContext* ctx, const float* vertices, const float* vertex_normals_or_NULL,
+                        int32_t num_vertices, MptRefitInfo* info_or_NULL);
+/* Downloads a BVH of the context as the kernels read it: which 0 the scene's, 1 the light-hit
+ * BVH's (counts of 0 when none is in use).  nodes: 80-byte Node8, tris: 48-byte TriRec records
+ * (csrc/bvh8.h; mpt.abi.NODE8_DTYPE / TRIREC_DTYPE).  out_counts (optional): nodes, records,
+ * levels.  With both caps 0 only the counts are returned. */
+int mpt_get_bvh(MptContext* ctx, int which, void* nodes, int64_t nodes_cap_bytes, void* tris, int64_t tris_cap_bytes,
+                int32_t* out_counts);
+/* No device needed: builds the BVH8 over build_vertices as mpt_upload_scene does, refits it to
+ * new_vertices with the host loop of csrc/refit.h (NULL: the builder's output unchanged) and
+ * returns the bytes mpt_get_bvh(ctx, 0, ...) returns after mpt_update_vertices -- except the
+ * records' two flag lanes (alpha test, material class), which a context stamps from its
+ * materials and which are 0 here. */
+int mpt_bvh_refit_host(const float* build_vertices, const float* new_vertices_or_NULL, int32_t num_vertices,
+                       const int32_t* indices, int32_t num_triangles, void* nodes, int64_t nodes_cap_bytes,
+                       void* tris, int64_t tris_cap_bytes, int32_t* out_counts);
 int mpt_set_envmap(MptContext* ctx, const float* rgba, int32_t width, int32_t height,
                    const float* alias_probas, const int32_t* alias_indices, float luminance_total_sum);
 /* Vose alias table in double precision, Image32Bit::compute_alias_table (Image/Image.cpp:579-659) */
