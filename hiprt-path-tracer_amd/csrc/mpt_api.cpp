@@ -176,6 +176,9 @@ struct MptContext {
     DBuf<float> nbox, nbox_light, tbox;
     double area0 = 0.0, area0_light = 0.0;
     bool mirrors_stale = false;
+    // mpt_rebuild_bvh (lbvh.hip) swapped in trees built on the device: the host copies' nodes,
+    // records and node boxes follow with the next refresh_mirrors (level_begin and depth at once)
+    bool topology_stale = false;
     std::vector<uint8_t> h_vert_used;
     int refit_host_loop = 0;              // test hook (MPT_REFIT_HOST): the refit by the host loop of refit.h
     int light_bvh = 1;                    // MPT_LIGHT_BVH at mpt_create: 0 = one closest-hit traversal per light-hit query
@@ -613,6 +616,25 @@ int ensure_paths(MptContext* c, int rx, int ry, int bh, int bi, int bc) {
 int refresh_mirrors(MptContext* c) {
     if (!c->mirrors_stale) return MPT_OK;
     hipStream_t st = c->stream;
+    if (c->topology_stale) {   // trees rebuilt on the device: sizes, nodes and exact boxes as well
+        const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
+        c->bvh.nodes.resize(c->nodes.n);
+        c->bvh.tris.resize(c->tris.n);
+        c->bvh.node_box.resize(c->nbox.n);
+        HIPCHK(hipMemcpyAsync(c->bvh.nodes.data(), c->nodes.p, c->nodes.n * sizeof(Node8), hipMemcpyDeviceToHost, st));
+        if (c->nbox.n == 6 * c->nodes.n)
+            HIPCHK(hipMemcpyAsync(c->bvh.node_box.data(), c->nbox.p, c->nbox.n * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (light) {
+            c->bvh_light.nodes.resize(c->nodes_light.n);
+            c->bvh_light.tris.resize(c->tris_light.n);
+            c->bvh_light.node_box.resize(c->nbox_light.n);
+            HIPCHK(hipMemcpyAsync(c->bvh_light.nodes.data(), c->nodes_light.p, c->nodes_light.n * sizeof(Node8), hipMemcpyDeviceToHost, st));
+            if (c->nbox_light.n == 6 * c->nodes_light.n)
+                HIPCHK(hipMemcpyAsync(c->bvh_light.node_box.data(), c->nbox_light.p, c->nbox_light.n * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        c->topology_stale = false;
+    }
     if (c->tris.n != c->bvh.tris.size() || c->pos.n != c->h_pos.size()) return fail(MPT_ERR_HIP, "refresh_mirrors: sizes differ");
     HIPCHK(hipMemcpyAsync(c->bvh.tris.data(), c->tris.p, c->tris.n * sizeof(TriRec), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(c->h_pos.data(), c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1149,6 +1171,7 @@ int mpt_upload_scene(MptContext* c, const MptScene* s) {
     c->box_pad = scene_box_pad(s->vertices, s->num_triangles, s->triangle_indices);
     c->area0 = node_box_area_sum(c->bvh.node_box.data(), c->bvh.nodes.size());
     c->mirrors_stale = false;
+    c->topology_stale = false;
     c->h_vert_used.assign((size_t)s->num_vertices, 0);
     for (size_t k = 0; k < 3 * (size_t)s->num_triangles; k++) c->h_vert_used[s->triangle_indices[k]] = 1;
     c->h_idx.assign(s->triangle_indices, s->triangle_indices + 3 * (size_t)s->num_triangles);
@@ -1253,7 +1276,9 @@ hipError_t update_vertices_device(MptContext* c, const float* v, const float* nr
     UV(c->nbox.alloc(6 * c->nodes.n));
     if (light) UV(c->nbox_light.alloc(6 * c->nodes_light.n));
     if (c->refit_host_loop) {
-        // (the host copies' w lanes are always current; their positions are rewritten here)
+        // (the host copies' w lanes are always current; their positions are rewritten here; after
+        // a rebuild on the device the copies first take the new trees)
+        if (c->topology_stale && refresh_mirrors(c) != MPT_OK) return hipErrorUnknown;
         std::vector<float> hb;
         refit_host(c->bvh, c->h_idx.data(), v, pad, hb);
         UV(hipMemcpyAsync(c->nodes.p, c->bvh.nodes.data(), c->nodes.n * sizeof(Node8), hipMemcpyHostToDevice, st));
@@ -1334,6 +1359,77 @@ int mpt_update_vertices(MptContext* c, const float* vertices, const float* verte
             r.light_levels = c->bvh_light.depth;
             r.light_area_ratio = (float)(node_box_area_sum(hbl.data(), c->nodes_light.n) / c->area0_light);
         }
+        *info = r;
+    }
+    return MPT_OK;
+}
+
+int mpt_rebuild_bvh(MptContext* c, MptRebuildInfo* info) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
+    const int n_prims = (int)c->mat_idx.n;
+    int stack_cap = MAX_STACK;   // as build_scene_bvh8
+    if (const char* e = std::getenv("MPT_BVH_MAX_STACK")) stack_cap = std::max(4, std::min(MAX_STACK, std::atoi(e)));
+    const int light_cap = std::min(MAX_STACK, c->light_bvh_max_stack);
+    LbvhDevice T, TL;
+    DBuf<int32_t> d_prims;
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = c->tbox.alloc(6 * std::max(c->tris.n, light ? c->tris_light.n : (size_t)0));
+    if (e == hipSuccess)
+        e = build_lbvh_device(nullptr, n_prims, n_prims, c->idx.p, c->pos.p, c->box_pad, c->tris.p, (int)c->tris.n, c->tbox.p, T, st);
+    if (e == hipSuccess && 2 * T.depth + 2 > stack_cap) {
+        free_lbvh(T);
+        return fail(MPT_ERR_UNSUPPORTED, "rebuilt BVH8 deeper than the traversal stack");
+    }
+    if (e == hipSuccess && light) {
+        e = d_prims.upload(c->h_light_prims.data(), c->h_light_prims.size(), st);
+        if (e == hipSuccess)
+            e = build_lbvh_device(d_prims.p, (int)c->h_light_prims.size(), n_prims, c->idx.p, c->pos.p, c->box_pad, c->tris_light.p,
+                                  (int)c->tris_light.n, c->tbox.p, TL, st);
+    }
+    std::vector<float> hb, hbl;
+    const bool light_fits = light && e == hipSuccess && 2 * TL.depth + 2 <= light_cap;
+    if (e == hipSuccess) {   // the new trees' area sums (MptRefitInfo::area_ratio is taken against them)
+        hb.resize(6 * (size_t)T.n_nodes);
+        e = hipMemcpy(hb.data(), T.nbox, hb.size() * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && light_fits) {
+            hbl.resize(6 * (size_t)TL.n_nodes);
+            e = hipMemcpy(hbl.data(), TL.nbox, hbl.size() * sizeof(float), hipMemcpyDeviceToHost);
+        }
+    }
+    if (e != hipSuccess) {
+        free_lbvh(T);
+        free_lbvh(TL);
+        (void)hipGetLastError();
+        c->has_scene = false;   // the caller uploads again
+        return fail(MPT_ERR_HIP, std::string("mpt_rebuild_bvh: ") + hipGetErrorString(e));
+    }
+    auto swap_in = [](DBuf<Node8>& dn, DBuf<TriRec>& dt, DBuf<float>& db, BVH8& h, LbvhDevice& t) {
+        dn.release(); dt.release(); db.release();
+        dn.p = t.nodes; dn.n = (size_t)t.n_nodes;
+        dt.p = t.tris; dt.n = (size_t)t.n_tris;
+        db.p = t.nbox; db.n = 6 * (size_t)t.n_nodes;
+        t.nodes = nullptr; t.tris = nullptr; t.nbox = nullptr;
+        h.level_begin = t.level_begin;
+        h.depth = t.depth;
+    };
+    swap_in(c->nodes, c->tris, c->nbox, c->bvh, T);
+    c->area0 = node_box_area_sum(hb.data(), (size_t)T.n_nodes);
+    if (light_fits) {
+        swap_in(c->nodes_light, c->tris_light, c->nbox_light, c->bvh_light, TL);
+        c->area0_light = node_box_area_sum(hbl.data(), (size_t)TL.n_nodes);
+    } else {
+        free_lbvh(TL);
+    }
+    c->mirrors_stale = true;
+    c->topology_stale = true;
+    if (info) {
+        MptRebuildInfo r{};
+        r.rebuilt = 1; r.nodes = T.n_nodes; r.records = T.n_tris; r.levels = T.depth;
+        if (light_fits) { r.light_rebuilt = 1; r.light_nodes = TL.n_nodes; r.light_records = TL.n_tris; r.light_levels = TL.depth; }
         *info = r;
     }
     return MPT_OK;

@@ -419,6 +419,20 @@ hipError_t launch_refit_levels(Node8* nodes, float* node_box, const float* tbox,
 int build_scene_bvh8(const float* vertices, const int32_t* indices, int32_t num_triangles, BVH8& out, int stack_limit);
 int copy_bvh_out(const Node8* nodes, size_t n_nodes, const TriRec* tris, size_t n_tris, int levels, void* out_nodes,
                  int64_t nodes_cap, void* out_tris, int64_t tris_cap, int32_t* out_counts);
+// lbvh.hip (lbvh.h): a BVH8 over the list d_prims (device, NULL: all n primitives in order) of n
+// of the scene's n_scene_prims primitives, built on the device from idx / pos into new buffers:
+// nodes, records (flag lanes carried over from old_tris per primitive) and exact node boxes, the
+// refit's bytes included (tbox: scratch of 6 n floats).  On an error nothing is left allocated.
+struct LbvhDevice {
+    Node8* nodes = nullptr;
+    TriRec* tris = nullptr;
+    float* nbox = nullptr;
+    int n_nodes = 0, n_tris = 0, depth = 0;
+    std::vector<int32_t> level_begin;
+};
+hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, const int32_t* idx, const float* pos, float pad,
+                             const TriRec* old_tris, int n_old, float* tbox, LbvhDevice& out, hipStream_t st);
+void free_lbvh(LbvhDevice& o);
 hipError_t launch_trace_raw(const DevScene& S, const float4* o, const float4* d, int n, bool any, float4* out_hit,
                             uint8_t* out_occ, int32_t* fetch_ctr, uint32_t* spill, int grid, hipStream_t st);
 

@@ -143,6 +143,11 @@ void GPURenderer::update_vertices(const float* vertices, const float* vertex_nor
     reset();   // samples, reservoirs and adaptive counters of the old geometry are stale
 }
 
+void GPURenderer::rebuild_bvh(MptRebuildInfo* info) {
+    for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_rebuild_bvh(m_ctxs[k], k == 0 ? info : nullptr));
+    // (no reset: results do not depend on the tree)
+}
+
 void GPURenderer::set_envmap(const float* rgba, int width, int height, const std::string& envmap_filepath) {
     // Image32Bit::compute_alias_table / compute_cdf (Image.cpp:553-659), restated in libmpt
     std::vector<float> prob((size_t)width * height), cdf((size_t)width * height);

@@ -127,6 +127,11 @@ public:
     // render carries need_to_reset, as after reset().  info (optional): the first context's report.
     void update_vertices(const float* vertices, const float* vertex_normals_or_null, int32_t num_vertices,
                          MptRefitInfo* info = nullptr);
+    // rebuild_bvh (no counterpart in the reference): every context rebuilds its BVHs on its GPU
+    // from the positions it holds (mpt_rebuild_bvh), e.g. once update_vertices reports a large
+    // area_ratio.  The accumulation continues: traversal results do not depend on the tree.
+    // info (optional): the first context's report.
+    void rebuild_bvh(MptRebuildInfo* info = nullptr);
     const std::vector<MptMaterial>& get_original_materials() const { return m_original_materials; }
     const std::vector<MptMaterial>& get_current_materials() const { return m_current_materials; }
 

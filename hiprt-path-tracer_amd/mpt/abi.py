@@ -460,6 +460,12 @@ class RefitInfo(C.Structure):
                 ("area_ratio", f32), ("light_area_ratio", f32)]
 
 
+class RebuildInfo(C.Structure):
+    """MptRebuildInfo: what mpt_rebuild_bvh reports (mpt.h)."""
+    _fields_ = [("rebuilt", i32), ("nodes", i32), ("records", i32), ("levels", i32),
+                ("light_rebuilt", i32), ("light_nodes", i32), ("light_records", i32), ("light_levels", i32)]
+
+
 # the BVH8 arrays of mpt_get_bvh / mpt_bvh_refit_host (csrc/bvh8.h): 80-byte nodes, 48-byte records
 NODE8_DTYPE = np.dtype([("p", "<f4", 3), ("e", "u1", 3), ("imask", "u1"), ("child_base", "<u4"), ("tri_base", "<u4"),
                         ("meta", "u1", 8), ("qlo", "u1", (3, 8)), ("qhi", "u1", (3, 8))])

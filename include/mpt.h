@@ -13,6 +13,8 @@
  *   mpt_update_materials          <- GPURenderer::update_materials (GPURenderer.h:228)
  *   mpt_update_vertices           <- (no counterpart: the reference rebuilds its HIPRT geometry) moved
  *                                    vertices with a GPU refit of both BVH8s
+ *   mpt_rebuild_bvh               <- (no counterpart: HIPRT rebuilds with the geometry) both BVH8s
+ *                                    rebuilt on the GPU from the positions on the device
  *   mpt_set_envmap                <- GPURenderer::set_envmap (GPURenderer.h:222, .cpp:1136-1174)
  *   mpt_set_luts                  <- GPURenderer::setup_brdfs_data (GPURenderer.h:76, .cpp:88-175)
  *   mpt_resize                    <- GPURenderer::resize (GPURenderer.h:172)
@@ -602,6 +604,35 @@ int mpt_get_bvh(MptContext* ctx, int which, void* nodes, int64_t nodes_cap_bytes
 int mpt_bvh_refit_host(const float* build_vertices, const float* new_vertices_or_NULL, int32_t num_vertices,
                        const int32_t* indices, int32_t num_triangles, void* nodes, int64_t nodes_cap_bytes,
                        void* tris, int64_t tris_cap_bytes, int32_t* out_counts);
+/* Rebuilds (DESIGN.md §2 "Rebuilds").  What mpt_rebuild_bvh reports: whether each tree was replaced
+ * (0 / 1) and the new tree's nodes, records and levels; light_*: the light-hit BVH (zeros when none
+ * is in use or it was left as it was). */
+typedef struct MptRebuildInfo {
+    int32_t rebuilt, nodes, records, levels;
+    int32_t light_rebuilt, light_nodes, light_records, light_levels;
+} MptRebuildInfo;
+/* Rebuilds the scene BVH, and the light-hit BVH when one is in use, on the GPU from the positions
+ * already on the device (after any mpt_update_vertices): Morton keys, a radix sort, Karras' radix
+ * tree, a greedy collapse to 8-wide nodes, then the refit's arithmetic on the new topology
+ * (csrc/lbvh.h).  The context's streams are drained; no vertices are uploaded and the host makes
+ * no pass over triangles or vertices.  A tree is built into new buffers and replaces the old one
+ * only when complete and when 2 * levels + 2 fits the traversal stack bound mpt_upload_scene uses;
+ * there is no shallower fallback.  A light-hit tree that does not fit is left as it was (refits
+ * kept it valid); when the scene tree does not fit the call returns MPT_ERR_UNSUPPORTED and changes
+ * nothing.  MPT_ERR_NO_SCENE without a scene.  MPT_ERR_HIP part-way through leaves the context
+ * without a scene: upload again.  Afterwards MptRefitInfo's area ratios are taken against the new
+ * trees (an identity update reports exactly 1), and mpt_get_bvh, mpt_update_vertices and
+ * mpt_update_materials work on the new trees.
+ * No frame reset is needed: traversal results never depend on the tree, so accumulation simply
+ * continues across a rebuild, bit for bit as without it. */
+int mpt_rebuild_bvh(MptContext* ctx, MptRebuildInfo* info_or_NULL);
+/* No device needed: the host loop of the same definition over the list prims (NULL: all
+ * num_triangles primitives in order; else num_prims > 0 scene primitive indices) -- the bytes
+ * mpt_get_bvh returns after mpt_rebuild_bvh, except the records' two flag lanes, which are 0 here
+ * as in mpt_bvh_refit_host.  The box pad is the whole scene's.  With both caps 0 only the counts. */
+int mpt_bvh_build_host(const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_triangles,
+                       const int32_t* prims_or_NULL, int32_t num_prims, void* nodes, int64_t nodes_cap_bytes, void* tris,
+                       int64_t tris_cap_bytes, int32_t* out_counts);
 int mpt_set_envmap(MptContext* ctx, const float* rgba, int32_t width, int32_t height,
                    const float* alias_probas, const int32_t* alias_indices, float luminance_total_sum);
 /* Vose alias table in double precision, Image32Bit::compute_alias_table (Image/Image.cpp:579-659) */
