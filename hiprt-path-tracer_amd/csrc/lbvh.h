@@ -11,6 +11,7 @@
 //             interleaved x, y, z from the top; the low 32 bits hold the list position
 //   order     ascending by key (keys are unique)
 //   tree      Karras' radix tree over the sorted keys; a node's box is the union of its range
+//             (MPT_BUILD_PLOC: the tree of ploc.h instead, over the same keys, with its own leaf order)
 //   collapse  breadth first: a subtree of at most LEAF_MAX triangles is a leaf slot; a node opens
 //             its non-leaf-slot child of the largest fp32 box area until it has 8 children
 //   slots     the octant heuristic of bvh8.cpp, with centres and costs in double
@@ -232,7 +233,10 @@ LBVH_FN void emit_node(const Tree& T, const int32_t slot[8], uint32_t child_base
 namespace mpt {
 // The host loop: the BVH8 over the list prims (NULL: the identity) of n_list primitives, with the
 // refit's bytes (refit_host) for pos and pad; the records' flag lanes are 0.
-void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims, int n_list, float pad, BVH8& out);
+// mode: MPT_BUILD_LBVH the radix tree above, MPT_BUILD_PLOC the binary tree of ploc.h (iterations:
+// optional, how many it took).
+void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims, int n_list, float pad, BVH8& out, int mode = 0,
+                     int* iterations = nullptr);
 }  // namespace mpt
 
 #undef LBVH_FN

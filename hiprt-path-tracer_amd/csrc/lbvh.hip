@@ -9,7 +9,8 @@
 //                     then the scatter with ranks from wave ballots (stable within the tile)
 //   k_scan_*          exclusive scan of 64-bit words: reduce per workgroup, scan of the partial
 //                     sums by one workgroup, scan per workgroup -- three launches
-//   k_radix_tree      one thread per internal node of Karras' radix tree
+//   k_radix_tree      one thread per internal node of Karras' radix tree (MPT_BUILD_PLOC: ploc.hip
+//                     builds the binary tree and its boxes instead; everything else is shared)
 //   k_box_round       one launch per round: a node whose children were finished by an earlier
 //                     launch (its stamp is set and smaller than this round's) takes their union
 //   k_collapse_count / k_collapse_emit   per breadth-first level: one thread per node chooses its
@@ -26,6 +27,7 @@
 #include <vector>
 
 #include "lbvh.h"
+#include "ploc.h"
 #include "mpt.h"
 #include "mpt_internal.h"
 
@@ -155,15 +157,6 @@ __global__ void __launch_bounds__(BLK) k_scan_down(uint64_t* __restrict__ a, int
     uint64_t total;
     const uint64_t e = block_excl_scan(i < n ? a[i] : 0, sh, &total);
     if (i < n) a[i] = partial[blockIdx.x] + e;
-}
-
-// a[0 .. n) -> its exclusive scan; the sum of all is left in partial[ceil(n / BLK)]
-hipError_t scan_u64(uint64_t* a, int n, uint64_t* partial, hipStream_t st) {
-    const int nb = (n + BLK - 1) / BLK;
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(BLK), 0, st, a, n, partial);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(BLK), 0, st, partial, nb);
-    hipLaunchKernelGGL(k_scan_down, dim3((unsigned)nb), dim3(BLK), 0, st, a, n, partial);
-    return hipGetLastError();
 }
 
 // ---- radix sort -------------------------------------------------------------------------
@@ -308,6 +301,15 @@ struct Scratch {
 
 }  // namespace
 
+// a[0 .. n) -> its exclusive scan; the sum of all is left in partial[ceil(n / BLK)]
+hipError_t scan_u64(uint64_t* a, int n, uint64_t* partial, hipStream_t st) {
+    const int nb = (n + BLK - 1) / BLK;
+    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(BLK), 0, st, a, n, partial);
+    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(BLK), 0, st, partial, nb);
+    hipLaunchKernelGGL(k_scan_down, dim3((unsigned)nb), dim3(BLK), 0, st, a, n, partial);
+    return hipGetLastError();
+}
+
 void free_lbvh(LbvhDevice& o) {
     if (o.nodes) (void)hipFree(o.nodes);
     if (o.tris) (void)hipFree(o.tris);
@@ -318,15 +320,18 @@ void free_lbvh(LbvhDevice& o) {
 #define LB(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { free_lbvh(out); return e_; } } while (0)
 
 hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, const int32_t* idx, const float* pos, float pad,
-                             const TriRec* old_tris, int n_old, float* tbox, LbvhDevice& out, hipStream_t st) {
+                             const TriRec* old_tris, int n_old, float* tbox, LbvhDevice& out, hipStream_t st, int mode,
+                             PlocStats* stats) {
     out = LbvhDevice{};
-    if (n <= 0) return hipErrorInvalidValue;
+    if (n <= 0 || (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC)) return hipErrorInvalidValue;
+    const bool ploc = mode == MPT_BUILD_PLOC && n > 1;
     const int cap = n / 2 + 1;                         // nodes: a node without internal children holds >= 4 triangles,
-                                                       // one with a single internal child 7 leaf slots (lbvh.h)
+                                                       // one with a single internal child 7 leaf slots (lbvh.h); the
+                                                       // argument uses no property of the radix tree: any binary tree
     const int n_int = n - 1;
     const int sort_blocks = (n + SORT_TILE - 1) / SORT_TILE;
     const int table_n = 256 * sort_blocks;
-    const int scan_max = std::max(table_n, cap);
+    const int scan_max = std::max(table_n, ploc ? n : cap);
     Scratch S;
     float* pbox = S.get<float>(6 * (size_t)n);
     double* bpart = S.get<double>(6 * (size_t)blocks(n) + 6);
@@ -344,6 +349,19 @@ hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, c
     int32_t* slots = S.get<int32_t>(8 * (size_t)cap);
     uint32_t* flags = S.get<uint32_t>(2 * (size_t)n_scene_prims);
     Node8* nodes = S.get<Node8>(cap);
+    PlocScratch PS{};
+    if (ploc) {
+        for (int k = 0; k < 2; k++) {
+            PS.cref[k] = S.get<int32_t>(n);
+            PS.ccnt[k] = S.get<int32_t>(n);
+            PS.cbox[k] = S.get<float>(6 * (size_t)n);
+        }
+        PS.mate = S.get<int32_t>(n);
+        PS.tail_info = S.get<int32_t>(mptploc::PLOC_TAIL + 2);
+        PS.words = table;
+        PS.partial = partial;
+        PS.count = stamp;
+    }
     LB(S.err);
     LB(hipMalloc(&out.tris, (size_t)n * sizeof(TriRec)));
 
@@ -368,10 +386,13 @@ hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, c
         cur ^= 1;
     }
     LB(hipGetLastError());
-    Tree T{left, right, first, last, bbox, pbox, pay[cur]};
+    Tree T{left, right, first, last, bbox, pbox, ploc ? pay[cur ^ 1] : pay[cur]};
     // tree and boxes
     int32_t root = ~0;
-    if (n_int > 0) {
+    if (ploc) {
+        root = n - 2;
+        LB(ploc_tree_device(n, pbox, pay[cur], left, right, first, last, bbox, pay[cur ^ 1], PS, st, stats));
+    } else if (n_int > 0) {
         root = 0;
         hipLaunchKernelGGL(k_radix_tree, dim3(blocks(n_int)), dim3(BLK), 0, st, code[cur], pay[cur], n, left, right, first, last, stamp);
         int32_t root_stamp = 0;
@@ -423,7 +444,8 @@ hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, c
 }
 #undef LB
 
-void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims, int n, float pad, BVH8& out) {
+void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims, int n, float pad, BVH8& out, int mode,
+                     int* iterations) {
     out = BVH8{};
     if (n <= 0) return;
     std::vector<float> pbox(6 * (size_t)n);
@@ -450,9 +472,17 @@ void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims,
     const int n_int = n - 1;
     std::vector<int32_t> left(n_int), right(n_int), first(n_int), last(n_int);
     std::vector<float> bbox(6 * (size_t)n_int);
-    Tree T{left.data(), right.data(), first.data(), last.data(), bbox.data(), pbox.data(), order.data()};
-    for (int i = 0; i < n_int; i++) radix_node(code.data(), order.data(), n, i, &left[i], &right[i], &first[i], &last[i]);
-    if (n_int > 0) {   // boxes: children before parents, by an explicit stack (min / max: exact in any order)
+    const bool ploc = mode == MPT_BUILD_PLOC && n > 1;
+    std::vector<uint32_t> order2(ploc ? n : 0);
+    Tree T{left.data(), right.data(), first.data(), last.data(), bbox.data(), pbox.data(), ploc ? order2.data() : order.data()};
+    if (iterations) *iterations = 0;
+    if (ploc) {
+        const int its = ploc_tree_host(n, pbox.data(), order.data(), left.data(), right.data(), first.data(), last.data(),
+                                       bbox.data(), order2.data());
+        if (iterations) *iterations = its;
+    }
+    for (int i = 0; i < n_int && !ploc; i++) radix_node(code.data(), order.data(), n, i, &left[i], &right[i], &first[i], &last[i]);
+    if (n_int > 0 && !ploc) {   // boxes: children before parents, by an explicit stack (min / max: exact in any order)
         std::vector<int32_t> stk{0}, post;
         while (!stk.empty()) {
             const int32_t x = stk.back();
@@ -468,7 +498,7 @@ void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims,
             for (int a = 0; a < 3; a++) { bbox[6 * (size_t)x + a] = b.lo[a]; bbox[6 * (size_t)x + 3 + a] = b.hi[a]; }
         }
     }
-    std::vector<int32_t> defs{n_int > 0 ? 0 : ~0}, next;
+    std::vector<int32_t> defs{ploc ? n - 2 : n_int > 0 ? 0 : ~0}, next;
     out.tris.resize(n);
     int begin = 0, rec_begin = 0;
     while (!defs.empty()) {
@@ -504,7 +534,15 @@ extern "C" {
 int mpt_bvh_build_host(const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_triangles,
                        const int32_t* prims, int32_t num_prims, void* nodes, int64_t nodes_cap_bytes, void* tris,
                        int64_t tris_cap_bytes, int32_t* out_counts) {
+    return mpt_bvh_build_host_mode(vertices, num_vertices, indices, num_triangles, prims, num_prims, MPT_BUILD_LBVH, nodes,
+                                   nodes_cap_bytes, tris, tris_cap_bytes, out_counts);
+}
+
+int mpt_bvh_build_host_mode(const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_triangles,
+                            const int32_t* prims, int32_t num_prims, int32_t mode, void* nodes, int64_t nodes_cap_bytes,
+                            void* tris, int64_t tris_cap_bytes, int32_t* out_counts) {
     using namespace mpt;
+    if (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC) return api_fail(MPT_ERR_INVALID_ARGUMENT, "bvh: unknown build mode");
     if (!vertices || !indices) return api_fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
     if (num_vertices <= 0 || num_triangles <= 0 || nodes_cap_bytes < 0 || tris_cap_bytes < 0)
         return api_fail(MPT_ERR_INVALID_ARGUMENT, "bvh: bad size");
@@ -516,7 +554,8 @@ int mpt_bvh_build_host(const float* vertices, int32_t num_vertices, const int32_
     for (int64_t i = 0; i < 3 * (int64_t)num_vertices; i++)
         if (!(std::fabs(vertices[i]) <= 3.4028234663852886e38f)) return api_fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
     BVH8 bvh;
-    build_lbvh_host(vertices, indices, prims, prims ? num_prims : num_triangles, scene_box_pad(vertices, num_triangles, indices), bvh);
+    build_lbvh_host(vertices, indices, prims, prims ? num_prims : num_triangles, scene_box_pad(vertices, num_triangles, indices), bvh,
+                    mode);
     return copy_bvh_out(bvh.nodes.data(), bvh.nodes.size(), bvh.tris.data(), bvh.tris.size(), bvh.depth, nodes, nodes_cap_bytes,
                         tris, tris_cap_bytes, out_counts);
 }

@@ -1364,8 +1364,11 @@ int mpt_update_vertices(MptContext* c, const float* vertices, const float* verte
     return MPT_OK;
 }
 
-int mpt_rebuild_bvh(MptContext* c, MptRebuildInfo* info) {
+int mpt_rebuild_bvh(MptContext* c, MptRebuildInfo* info) { return mpt_rebuild_bvh_mode(c, MPT_BUILD_LBVH, info); }
+
+int mpt_rebuild_bvh_mode(MptContext* c, int32_t mode, MptRebuildInfo* info) {
     if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC) return fail(MPT_ERR_INVALID_ARGUMENT, "bvh: unknown build mode");
     if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -1375,11 +1378,13 @@ int mpt_rebuild_bvh(MptContext* c, MptRebuildInfo* info) {
     if (const char* e = std::getenv("MPT_BVH_MAX_STACK")) stack_cap = std::max(4, std::min(MAX_STACK, std::atoi(e)));
     const int light_cap = std::min(MAX_STACK, c->light_bvh_max_stack);
     LbvhDevice T, TL;
+    PlocStats ps, psl;
     DBuf<int32_t> d_prims;
     hipError_t e = drain(c);
     if (e == hipSuccess) e = c->tbox.alloc(6 * std::max(c->tris.n, light ? c->tris_light.n : (size_t)0));
     if (e == hipSuccess)
-        e = build_lbvh_device(nullptr, n_prims, n_prims, c->idx.p, c->pos.p, c->box_pad, c->tris.p, (int)c->tris.n, c->tbox.p, T, st);
+        e = build_lbvh_device(nullptr, n_prims, n_prims, c->idx.p, c->pos.p, c->box_pad, c->tris.p, (int)c->tris.n, c->tbox.p, T, st,
+                              mode, &ps);
     if (e == hipSuccess && 2 * T.depth + 2 > stack_cap) {
         free_lbvh(T);
         return fail(MPT_ERR_UNSUPPORTED, "rebuilt BVH8 deeper than the traversal stack");
@@ -1388,7 +1393,7 @@ int mpt_rebuild_bvh(MptContext* c, MptRebuildInfo* info) {
         e = d_prims.upload(c->h_light_prims.data(), c->h_light_prims.size(), st);
         if (e == hipSuccess)
             e = build_lbvh_device(d_prims.p, (int)c->h_light_prims.size(), n_prims, c->idx.p, c->pos.p, c->box_pad, c->tris_light.p,
-                                  (int)c->tris_light.n, c->tbox.p, TL, st);
+                                  (int)c->tris_light.n, c->tbox.p, TL, st, mode, &psl);
     }
     std::vector<float> hb, hbl;
     const bool light_fits = light && e == hipSuccess && 2 * TL.depth + 2 <= light_cap;
@@ -1426,6 +1431,9 @@ int mpt_rebuild_bvh(MptContext* c, MptRebuildInfo* info) {
     }
     c->mirrors_stale = true;
     c->topology_stale = true;
+    if (mode == MPT_BUILD_PLOC && std::getenv("MPT_PLOC_STATS"))   // (a measuring aid: tools/rebuild_time.py)
+        std::fprintf(stderr, "mpt ploc: scene iterations %d tail %d, light iterations %d tail %d\n", ps.iterations,
+                     ps.tail_iterations, psl.iterations, psl.tail_iterations);
     if (info) {
         MptRebuildInfo r{};
         r.rebuilt = 1; r.nodes = T.n_nodes; r.records = T.n_tris; r.levels = T.depth;

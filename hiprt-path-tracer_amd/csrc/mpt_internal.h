@@ -430,9 +430,33 @@ struct LbvhDevice {
     int n_nodes = 0, n_tris = 0, depth = 0;
     std::vector<int32_t> level_begin;
 };
+// mode: MPT_BUILD_LBVH (Karras' radix tree) or MPT_BUILD_PLOC (ploc.h); stats: optional, mode 1
+struct PlocStats {
+    int iterations = 0, tail_iterations = 0;
+};
 hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, const int32_t* idx, const float* pos, float pad,
-                             const TriRec* old_tris, int n_old, float* tbox, LbvhDevice& out, hipStream_t st);
+                             const TriRec* old_tris, int n_old, float* tbox, LbvhDevice& out, hipStream_t st, int mode = 0,
+                             PlocStats* stats = nullptr);
 void free_lbvh(LbvhDevice& o);
+// lbvh.hip: a[0 .. n) -> its exclusive scan; the sum of all is left in partial[ceil(n / 256)]
+hipError_t scan_u64(uint64_t* a, int n, uint64_t* partial, hipStream_t st);
+// ploc.hip (ploc.h): the PLOC tree over n >= 2 sorted positions into left / right / first / last /
+// nbox (n - 1 nodes) and the new order; scratch from the caller: two cluster lists of n entries
+// (reference, count, six box planes of n floats), per position what becomes of it and the scan's
+// word, the scan's partial sums, a count per node and the tail's report
+struct PlocScratch {
+    int32_t* cref[2];
+    int32_t* ccnt[2];
+    float* cbox[2];
+    int32_t* mate;
+    uint64_t* words;
+    uint64_t* partial;
+    int32_t* count;
+    int32_t* tail_info;      // PLOC_TAIL + 2 words
+};
+hipError_t ploc_tree_device(int n, const float* pbox, const uint32_t* order, int32_t* left, int32_t* right, int32_t* first,
+                            int32_t* last, float* nbox, uint32_t* order_out, const PlocScratch& B, hipStream_t st,
+                            PlocStats* stats);
 hipError_t launch_trace_raw(const DevScene& S, const float4* o, const float4* d, int n, bool any, float4* out_hit,
                             uint8_t* out_occ, int32_t* fetch_ctr, uint32_t* spill, int grid, hipStream_t st);
 

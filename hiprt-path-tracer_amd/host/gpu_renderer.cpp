@@ -143,8 +143,8 @@ void GPURenderer::update_vertices(const float* vertices, const float* vertex_nor
     reset();   // samples, reservoirs and adaptive counters of the old geometry are stale
 }
 
-void GPURenderer::rebuild_bvh(MptRebuildInfo* info) {
-    for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_rebuild_bvh(m_ctxs[k], k == 0 ? info : nullptr));
+void GPURenderer::rebuild_bvh(MptRebuildInfo* info, int32_t mode) {
+    for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_rebuild_bvh_mode(m_ctxs[k], mode, k == 0 ? info : nullptr));
     // (no reset: results do not depend on the tree)
 }
 

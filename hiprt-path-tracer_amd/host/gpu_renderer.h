@@ -128,10 +128,11 @@ public:
     void update_vertices(const float* vertices, const float* vertex_normals_or_null, int32_t num_vertices,
                          MptRefitInfo* info = nullptr);
     // rebuild_bvh (no counterpart in the reference): every context rebuilds its BVHs on its GPU
-    // from the positions it holds (mpt_rebuild_bvh), e.g. once update_vertices reports a large
+    // from the positions it holds (mpt_rebuild_bvh_mode), e.g. once update_vertices reports a large
     // area_ratio.  The accumulation continues: traversal results do not depend on the tree.
-    // info (optional): the first context's report.
-    void rebuild_bvh(MptRebuildInfo* info = nullptr);
+    // info (optional): the first context's report.  mode: MPT_BUILD_LBVH, or MPT_BUILD_PLOC for a
+    // better tree from a slower build.
+    void rebuild_bvh(MptRebuildInfo* info = nullptr, int32_t mode = MPT_BUILD_LBVH);
     const std::vector<MptMaterial>& get_original_materials() const { return m_original_materials; }
     const std::vector<MptMaterial>& get_current_materials() const { return m_current_materials; }
 

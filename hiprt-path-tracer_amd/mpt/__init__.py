@@ -36,6 +36,7 @@ SYMBOLS = [
     "mpt_display_settings_default", "mpt_display_uniforms", "mpt_display", "mpt_display_host", "mpt_write_png",
     "mpt_denoise_settings_default", "mpt_denoise", "mpt_denoised_buffer", "mpt_denoise_device", "mpt_denoise_host",
     "mpt_update_vertices", "mpt_get_bvh", "mpt_bvh_refit_host", "mpt_rebuild_bvh", "mpt_bvh_build_host",
+    "mpt_rebuild_bvh_mode", "mpt_bvh_build_host_mode",
 ]
 
 
@@ -120,6 +121,8 @@ def lib() -> C.CDLL:
     L.mpt_bvh_refit_host.argtypes = [vp, vp, i32, vp, i32, vp, C.c_int64, vp, C.c_int64, vp]
     L.mpt_rebuild_bvh.argtypes = [vp, C.POINTER(abi.RebuildInfo)]
     L.mpt_bvh_build_host.argtypes = [vp, i32, vp, i32, vp, i32, vp, C.c_int64, vp, C.c_int64, vp]
+    L.mpt_rebuild_bvh_mode.argtypes = [vp, i32, C.POINTER(abi.RebuildInfo)]
+    L.mpt_bvh_build_host_mode.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64, vp, C.c_int64, vp]
     _lib = L
     return L
 
@@ -304,17 +307,19 @@ def bvh_refit_host(build_vertices, indices, new_vertices=None):
                                                                       n, nc, t, tc, cnt))
 
 
-def bvh_build_host(vertices, indices, prims=None):
-    """mpt_bvh_build_host, no GPU: the BVH8 a rebuild makes (csrc/lbvh.h) over vertices ([V, 3]
-    float32) and indices ([T, 3] int32), over all triangles or over the scene primitives listed in
-    prims.  Returns (nodes, tris, levels) as bvh_refit_host does: the bytes GPURenderer.get_bvh
-    returns after rebuild_bvh (the records' flag lanes are 0 here)."""
+def bvh_build_host(vertices, indices, prims=None, mode=abi.BUILD_LBVH):
+    """mpt_bvh_build_host_mode, no GPU: the BVH8 a rebuild makes (csrc/lbvh.h; mode abi.BUILD_PLOC:
+    with the binary tree of csrc/ploc.h) over vertices ([V, 3] float32) and indices ([T, 3] int32),
+    over all triangles or over the scene primitives listed in prims.  Returns (nodes, tris, levels)
+    as bvh_refit_host does: the bytes GPURenderer.get_bvh returns after rebuild_bvh(mode=mode) (the
+    records' flag lanes are 0 here)."""
     v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
     idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
     pr = None if prims is None else np.ascontiguousarray(prims, np.int32).reshape(-1)
     L = lib()
-    return _bvh_arrays(lambda n, nc, t, tc, cnt: L.mpt_bvh_build_host(_p(v), v.shape[0], _p(idx), idx.shape[0], _p(pr),
-                                                                      0 if pr is None else pr.shape[0], n, nc, t, tc, cnt))
+    return _bvh_arrays(lambda n, nc, t, tc, cnt: L.mpt_bvh_build_host_mode(_p(v), v.shape[0], _p(idx), idx.shape[0], _p(pr),
+                                                                           0 if pr is None else pr.shape[0], int(mode),
+                                                                           n, nc, t, tc, cnt))
 
 
 class GPURenderer:
@@ -355,11 +360,12 @@ class GPURenderer:
         _check(lib().mpt_update_vertices(self.h, _p(v), _p(n), v.shape[0], C.byref(ri) if info else None))
         return ri
 
-    def rebuild_bvh(self, info=False):
-        """mpt_rebuild_bvh: both BVHs rebuilt on the GPU from the positions on the device.  No
+    def rebuild_bvh(self, info=False, mode=abi.BUILD_LBVH):
+        """mpt_rebuild_bvh_mode: both BVHs rebuilt on the GPU from the positions on the device, as
+        an LBVH (abi.BUILD_LBVH) or by PLOC (abi.BUILD_PLOC: a better tree, a slower build).  No
         frame reset is needed.  info=True returns the abi.RebuildInfo, else None."""
         ri = abi.RebuildInfo() if info else None
-        _check(lib().mpt_rebuild_bvh(self.h, C.byref(ri) if info else None))
+        _check(lib().mpt_rebuild_bvh_mode(self.h, int(mode), C.byref(ri) if info else None))
         return ri
 
     def get_bvh(self, which=0):

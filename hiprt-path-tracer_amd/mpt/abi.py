@@ -460,8 +460,11 @@ class RefitInfo(C.Structure):
                 ("area_ratio", f32), ("light_area_ratio", f32)]
 
 
+BUILD_LBVH, BUILD_PLOC = 0, 1   # MPT_BUILD_*: the build modes of mpt_rebuild_bvh_mode
+
+
 class RebuildInfo(C.Structure):
-    """MptRebuildInfo: what mpt_rebuild_bvh reports (mpt.h)."""
+    """MptRebuildInfo: what mpt_rebuild_bvh / mpt_rebuild_bvh_mode report (mpt.h)."""
     _fields_ = [("rebuilt", i32), ("nodes", i32), ("records", i32), ("levels", i32),
                 ("light_rebuilt", i32), ("light_nodes", i32), ("light_records", i32), ("light_levels", i32)]
 

@@ -14,7 +14,9 @@
  *   mpt_update_vertices           <- (no counterpart: the reference rebuilds its HIPRT geometry) moved
  *                                    vertices with a GPU refit of both BVH8s
  *   mpt_rebuild_bvh               <- (no counterpart: HIPRT rebuilds with the geometry) both BVH8s
- *                                    rebuilt on the GPU from the positions on the device
+ *   mpt_rebuild_bvh_mode             rebuilt on the GPU from the positions on the device: an LBVH
+ *                                    (mode 0, the default) or PLOC (mode 1; the reference builds with
+ *                                    hiprtBuildFlagBitPreferHighQualityBuild)
  *   mpt_set_envmap                <- GPURenderer::set_envmap (GPURenderer.h:222, .cpp:1136-1174)
  *   mpt_set_luts                  <- GPURenderer::setup_brdfs_data (GPURenderer.h:76, .cpp:88-175)
  *   mpt_resize                    <- GPURenderer::resize (GPURenderer.h:172)
@@ -626,6 +628,18 @@ typedef struct MptRebuildInfo {
  * No frame reset is needed: traversal results never depend on the tree, so accumulation simply
  * continues across a rebuild, bit for bit as without it. */
 int mpt_rebuild_bvh(MptContext* ctx, MptRebuildInfo* info_or_NULL);
+/* The build modes of a rebuild.  MPT_BUILD_LBVH: Karras' radix tree as above (what mpt_rebuild_bvh
+ * builds).  MPT_BUILD_PLOC: the binary tree comes from parallel locally-ordered clustering over the
+ * same Morton order instead (csrc/ploc.h: radius 8, mutual nearest neighbours by the fp32 area of
+ * the union merge, iterated until one cluster is left); keys, sort, collapse, slots, layout, flag
+ * lanes and refit are the same code.  A lower-area tree for more build time. */
+#define MPT_BUILD_LBVH 0
+#define MPT_BUILD_PLOC 1
+/* mpt_rebuild_bvh with a build mode for both trees; mode 0 is mpt_rebuild_bvh, byte for byte.  An
+ * unknown mode returns MPT_ERR_INVALID_ARGUMENT and changes nothing.  Every other rule of
+ * mpt_rebuild_bvh holds as stated there.  MPT_PLOC_TAIL=0 in the environment (read at the call)
+ * keeps mode 1 from finishing its last 1024 clusters in one workgroup: the same bytes, slower. */
+int mpt_rebuild_bvh_mode(MptContext* ctx, int32_t mode, MptRebuildInfo* info_or_NULL);
 /* No device needed: the host loop of the same definition over the list prims (NULL: all
  * num_triangles primitives in order; else num_prims > 0 scene primitive indices) -- the bytes
  * mpt_get_bvh returns after mpt_rebuild_bvh, except the records' two flag lanes, which are 0 here
@@ -633,6 +647,10 @@ int mpt_rebuild_bvh(MptContext* ctx, MptRebuildInfo* info_or_NULL);
 int mpt_bvh_build_host(const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_triangles,
                        const int32_t* prims_or_NULL, int32_t num_prims, void* nodes, int64_t nodes_cap_bytes, void* tris,
                        int64_t tris_cap_bytes, int32_t* out_counts);
+/* mpt_bvh_build_host with a build mode: the bytes after mpt_rebuild_bvh_mode(ctx, mode, ...). */
+int mpt_bvh_build_host_mode(const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_triangles,
+                            const int32_t* prims_or_NULL, int32_t num_prims, int32_t mode, void* nodes,
+                            int64_t nodes_cap_bytes, void* tris, int64_t tris_cap_bytes, int32_t* out_counts);
 int mpt_set_envmap(MptContext* ctx, const float* rgba, int32_t width, int32_t height,
                    const float* alias_probas, const int32_t* alias_indices, float luminance_total_sum);
 /* Vose alias table in double precision, Image32Bit::compute_alias_table (Image/Image.cpp:579-659) */

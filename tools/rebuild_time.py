@@ -17,7 +17,13 @@ after the timed repeats.  Writes one JSON document (--out) and prints it.
 --upload-only times just the uploads: the run to make at a commit without mpt_rebuild_bvh, with
 --pkg naming that commit's package directory.
 --variant rebuild runs `--calls` rebuilds and nothing else: the run to put under
-`rocprofv3 --kernel-trace --stats` for per-kernel times."""
+`rocprofv3 --kernel-trace --stats` for per-kernel times.
+--mode 1 adds the PLOC build mode (mpt_rebuild_bvh_mode, MPT_BUILD_PLOC): its rebuild is timed next
+to the LBVH's inside every repeat, a fourth context `rebuilt_ploc` joins the render columns, and
+the iteration counts of both trees (and how many ran in the single-workgroup tail) are taken from
+the library's MPT_PLOC_STATS line of one extra call.  With --variant rebuild the calls use the mode.
+--rebuild-only times just the rebuilds (of --mode 0, and of mode 1 when given): the run to make
+with --pkg at a commit that has mpt_rebuild_bvh only, to show that mode 0 has not moved."""
 import argparse
 import copy
 import ctypes as C
@@ -43,6 +49,8 @@ def main():
     ap.add_argument("--blocks", type=int, default=0, help="0: the C3 city; else a smaller city of that many blocks")
     ap.add_argument("--sets", default="identity,jitter_1pct", help="vertex sets of the render columns (also: jitter_x10)")
     ap.add_argument("--upload-only", action="store_true")
+    ap.add_argument("--rebuild-only", action="store_true")
+    ap.add_argument("--mode", type=int, default=0, help="1: also the PLOC build mode")
     ap.add_argument("--variant", default=None)
     ap.add_argument("--pkg", default=os.path.join(ROOT, "hiprt-path-tracer_amd"))
     ap.add_argument("--out", default=None)
@@ -91,12 +99,13 @@ def main():
         out["upload_wall_ms"] = {k: stats(t) for k, t in ts.items()}
         return finish(a, out)
 
-    def rebuild_ms(r):
+    def rebuild_ms(r, mode=0):
+        kw = {"mode": mode} if mode else {}                # (a package without build modes takes none)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         r.synchronize_kernel()
         e0.record(stream)
         t0 = time.perf_counter()
-        ri = r.rebuild_bvh(info=True)
+        ri = r.rebuild_bvh(info=True, **kw)
         wall = (time.perf_counter() - t0) * 1e3
         e1.record(stream)
         e1.synchronize()
@@ -107,8 +116,47 @@ def main():
             r.set_scene(sd0)
             r.update_vertices(v1)
             for k in range(a.calls):
-                r.rebuild_bvh()
+                r.rebuild_bvh(**({"mode": a.mode} if a.mode else {}))
         return
+
+    def ploc_stats(r):
+        """The library's report of one mode-1 rebuild (a line on stderr under MPT_PLOC_STATS)."""
+        import re
+        import tempfile
+        with tempfile.TemporaryFile() as tmp:
+            sys.stderr.flush()
+            saved = os.dup(2)
+            os.dup2(tmp.fileno(), 2)
+            os.environ["MPT_PLOC_STATS"] = "1"
+            try:
+                r.rebuild_bvh(mode=1)
+            finally:
+                del os.environ["MPT_PLOC_STATS"]
+                os.dup2(saved, 2)
+                os.close(saved)
+            tmp.seek(0)
+            m = re.search(r"scene iterations (\d+) tail (\d+), light iterations (\d+) tail (\d+)", tmp.read().decode())
+        return dict(zip(("iterations", "tail_iterations", "light_iterations", "light_tail_iterations"), map(int, m.groups())))
+
+    modes = (0, 1) if a.mode else (0,)
+    if a.rebuild_only:
+        with mpt.GPURenderer(0, stream=stream.cuda_stream) as r:
+            r.set_scene(sd0)
+            r.update_vertices(v1)
+            ts = {m: ([], []) for m in modes}
+            for m in modes:
+                rebuild_ms(r, m)                           # warm-up
+            for _ in range(a.repeats):
+                for m in modes:
+                    w, g, info = rebuild_ms(r, m)
+                    ts[m][0].append(w)
+                    ts[m][1].append(g)
+            for m in modes:
+                key = "rebuild_ploc" if m else "rebuild"
+                out[key + "_wall_ms"], out[key + "_gpu_ms"] = stats(ts[m][0]), stats(ts[m][1])
+            if a.mode:
+                out["ploc"] = ploc_stats(r)
+        return finish(a, out)
 
     W, H = 1920, 1080
     luts = scene.load_luts()
@@ -148,10 +196,10 @@ def main():
             sets[name] = v10
         else:
             sets[name] = {"identity": v0, "jitter_1pct": v1}[name]
-    cols = ("rebuilt_gpu", "fresh_upload", "refitted")
+    cols = ("rebuilt_gpu", "fresh_upload", "refitted") + (("rebuilt_ploc",) if a.mode else ())
     with mpt.GPURenderer(0, stream=stream.cuda_stream) as rb, mpt.GPURenderer(0, stream=stream.cuda_stream) as rf, \
-            mpt.GPURenderer(0, stream=stream.cuda_stream) as rr:
-        ctx = dict(zip(cols, (rb, rf, rr)))
+            mpt.GPURenderer(0, stream=stream.cuda_stream) as rr, mpt.GPURenderer(0, stream=stream.cuda_stream) as rp:
+        ctx = dict(zip(cols, (rb, rf, rr, rp)))
         for r in ctx.values():
             r.set_scene(sd0)
             r.set_luts(luts)
@@ -159,6 +207,10 @@ def main():
             render_ms(r)                                   # warm-up: path state allocated, kernels loaded
         rb.update_vertices(v1)
         rebuild_ms(rb)                                     # warm-up
+        t_wall_p, t_gpu_p, info_p = [], [], None
+        if a.mode:
+            rp.update_vertices(v1)
+            rebuild_ms(rp, 1)
         t_wall, t_gpu, t_upload = [], [], []
         t_render = {name: {c: [] for c in cols} for name in sets}
         info = None
@@ -167,10 +219,18 @@ def main():
             w, g, info = rebuild_ms(rb)
             t_wall.append(w)
             t_gpu.append(g)
+            if a.mode:
+                rp.update_vertices(v1)
+                w, g, info_p = rebuild_ms(rp, 1)
+                t_wall_p.append(w)
+                t_gpu_p.append(g)
             t_upload.append(upload_ms(rf, with_vertices(v1)))
             for name, v in sets.items():
                 rb.update_vertices(v)
                 rb.rebuild_bvh()
+                if a.mode:
+                    rp.update_vertices(v)
+                    rp.rebuild_bvh(mode=1)
                 upload_ms(rf, with_vertices(v))
                 rr.update_vertices(v)
                 for c in cols:
@@ -183,10 +243,19 @@ def main():
         out["rebuild_gpu_ms"] = stats(t_gpu)
         out["upload_wall_ms"] = stats(t_upload)
         out["upload_over_rebuild"] = round(out["upload_wall_ms"]["median"] / out["rebuild_wall_ms"]["median"], 1)
+        if a.mode:
+            rp.update_vertices(v1)
+            out["ploc"] = dict(ploc_stats(rp), nodes=info_p.nodes, levels=info_p.levels, light_nodes=info_p.light_nodes,
+                               light_levels=info_p.light_levels)
+            out["rebuild_ploc_wall_ms"] = stats(t_wall_p)
+            out["rebuild_ploc_gpu_ms"] = stats(t_gpu_p)
         out["render"] = {"width": W, "height": H, "samples": a.samples, "batch": a.batch, "unit": "wall ms per sample"}
         for name, v in sets.items():
             rb.update_vertices(v)
             rb.rebuild_bvh()
+            if a.mode:
+                rp.update_vertices(v)
+                rp.rebuild_bvh(mode=1)
             upload_ms(rf, with_vertices(v))
             ri = rr.update_vertices(v, info=True)
             out["render"][name] = {c: dict(stats(t_render[name][c]), **per_ray(ctx[c])) for c in cols}
