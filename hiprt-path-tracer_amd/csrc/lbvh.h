@@ -11,7 +11,8 @@
 //             interleaved x, y, z from the top; the low 32 bits hold the list position
 //   order     ascending by key (keys are unique)
 //   tree      Karras' radix tree over the sorted keys; a node's box is the union of its range
-//             (MPT_BUILD_PLOC: the tree of ploc.h instead, over the same keys, with its own leaf order)
+//             (MPT_BUILD_PLOC: the tree of ploc.h instead, over the same keys, with its own leaf order;
+//             MPT_BUILD_SAH: the tree of sah.h, likewise)
 //   collapse  breadth first: a subtree of at most LEAF_MAX triangles is a leaf slot; a node opens
 //             its non-leaf-slot child of the largest fp32 box area until it has 8 children
 //   slots     the octant heuristic of bvh8.cpp, with centres and costs in double
@@ -234,7 +235,7 @@ namespace mpt {
 // The host loop: the BVH8 over the list prims (NULL: the identity) of n_list primitives, with the
 // refit's bytes (refit_host) for pos and pad; the records' flag lanes are 0.
 // mode: MPT_BUILD_LBVH the radix tree above, MPT_BUILD_PLOC the binary tree of ploc.h (iterations:
-// optional, how many it took).
+// optional, how many it took), MPT_BUILD_SAH the binary tree of sah.h (iterations: its levels).
 void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims, int n_list, float pad, BVH8& out, int mode = 0,
                      int* iterations = nullptr);
 }  // namespace mpt

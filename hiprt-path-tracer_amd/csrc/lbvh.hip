@@ -9,8 +9,9 @@
 //                     then the scatter with ranks from wave ballots (stable within the tile)
 //   k_scan_*          exclusive scan of 64-bit words: reduce per workgroup, scan of the partial
 //                     sums by one workgroup, scan per workgroup -- three launches
-//   k_radix_tree      one thread per internal node of Karras' radix tree (MPT_BUILD_PLOC: ploc.hip
-//                     builds the binary tree and its boxes instead; everything else is shared)
+//   k_radix_tree      one thread per internal node of Karras' radix tree (MPT_BUILD_PLOC: ploc.hip,
+//                     MPT_BUILD_SAH: sah.hip builds the binary tree and its boxes instead; everything
+//                     else is shared)
 //   k_box_round       one launch per round: a node whose children were finished by an earlier
 //                     launch (its stamp is set and smaller than this round's) takes their union
 //   k_collapse_count / k_collapse_emit   per breadth-first level: one thread per node chooses its
@@ -28,6 +29,7 @@
 
 #include "lbvh.h"
 #include "ploc.h"
+#include "sah.h"
 #include "mpt.h"
 #include "mpt_internal.h"
 
@@ -323,15 +325,16 @@ hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, c
                              const TriRec* old_tris, int n_old, float* tbox, LbvhDevice& out, hipStream_t st, int mode,
                              PlocStats* stats) {
     out = LbvhDevice{};
-    if (n <= 0 || (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC)) return hipErrorInvalidValue;
+    if (n <= 0 || (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC && mode != MPT_BUILD_SAH)) return hipErrorInvalidValue;
     const bool ploc = mode == MPT_BUILD_PLOC && n > 1;
+    const bool sah = mode == MPT_BUILD_SAH && n > LEAF_MAX;   // (up to LEAF_MAX: one leaf slot whatever the tree, the radix tree's path)
     const int cap = n / 2 + 1;                         // nodes: a node without internal children holds >= 4 triangles,
                                                        // one with a single internal child 7 leaf slots (lbvh.h); the
                                                        // argument uses no property of the radix tree: any binary tree
     const int n_int = n - 1;
     const int sort_blocks = (n + SORT_TILE - 1) / SORT_TILE;
     const int table_n = 256 * sort_blocks;
-    const int scan_max = std::max(table_n, ploc ? n : cap);
+    const int scan_max = std::max(table_n, sah ? n + 1 : ploc ? n : cap);
     Scratch S;
     float* pbox = S.get<float>(6 * (size_t)n);
     double* bpart = S.get<double>(6 * (size_t)blocks(n) + 6);
@@ -362,6 +365,29 @@ hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, c
         PS.partial = partial;
         PS.count = stamp;
     }
+    SahScratch SS{};
+    if (sah) {
+        SS.tail = sah_tail_from_env();
+        SS.big_slots = SS.tail > 0 ? n / SS.tail + 1 : n;
+        SS.list_cap = n / 2 + 1;
+        for (int k = 0; k < 2; k++) {
+            SS.nid[k] = S.get<int32_t>(n);
+            SS.lfirst[k] = S.get<int32_t>(SS.list_cap);
+            SS.llast[k] = S.get<int32_t>(SS.list_cap);
+            SS.lpslot[k] = S.get<int32_t>(SS.list_cap);
+        }
+        SS.dec = S.get<int32_t>(SS.list_cap);
+        SS.nmid = S.get<int32_t>(SS.list_cap);
+        SS.nB = S.get<float>(6 * (size_t)SS.list_cap);
+        SS.nCB = S.get<double>(6 * (size_t)SS.list_cap);
+        SS.cw = S.get<uint64_t>(SS.list_cap);
+        SS.words = table;
+        SS.partial = partial;
+        SS.gB = S.get<uint32_t>(6 * (size_t)SS.big_slots);
+        SS.gCB = S.get<uint64_t>(6 * (size_t)SS.big_slots);
+        SS.gbins = S.get<uint32_t>((size_t)mptsah::BIN_WORDS * SS.big_slots);
+        SS.report = S.get<int32_t>(2);
+    }
     LB(S.err);
     LB(hipMalloc(&out.tris, (size_t)n * sizeof(TriRec)));
 
@@ -389,7 +415,13 @@ hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, c
     Tree T{left, right, first, last, bbox, pbox, ploc ? pay[cur ^ 1] : pay[cur]};
     // tree and boxes
     int32_t root = ~0;
-    if (ploc) {
+    if (sah) {
+        int at = cur;
+        SahStats ss;
+        LB(sah_tree_device(n, pbox, pay, cur, left, right, first, last, bbox, SS, st, &root, &at, &ss));
+        T.order = pay[at];
+        if (stats) { stats->iterations = ss.levels; stats->tail_iterations = ss.levels - ss.grid_levels; }
+    } else if (ploc) {
         root = n - 2;
         LB(ploc_tree_device(n, pbox, pay[cur], left, right, first, last, bbox, pay[cur ^ 1], PS, st, stats));
     } else if (n_int > 0) {
@@ -472,10 +504,19 @@ void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims,
     const int n_int = n - 1;
     std::vector<int32_t> left(n_int), right(n_int), first(n_int), last(n_int);
     std::vector<float> bbox(6 * (size_t)n_int);
-    const bool ploc = mode == MPT_BUILD_PLOC && n > 1;
+    const bool sah = mode == MPT_BUILD_SAH && n > 1;
+    const bool ploc = (mode == MPT_BUILD_PLOC && n > 1) || sah;       // (below: a tree with its own order and root)
     std::vector<uint32_t> order2(ploc ? n : 0);
     Tree T{left.data(), right.data(), first.data(), last.data(), bbox.data(), pbox.data(), ploc ? order2.data() : order.data()};
     if (iterations) *iterations = 0;
+    int32_t sah_root = NO_REF;
+    if (sah) {
+        int levels = 0;
+        sah_root = sah_tree_host(n, pbox.data(), order.data(), sah_depth_from_env(), left.data(), right.data(), first.data(),
+                                 last.data(), bbox.data(), order2.data(), &levels);
+        if (iterations) *iterations = levels;
+        if (sah_root == NO_REF) return;                // (never by sah.h: an empty tree is the report)
+    } else
     if (ploc) {
         const int its = ploc_tree_host(n, pbox.data(), order.data(), left.data(), right.data(), first.data(), last.data(),
                                        bbox.data(), order2.data());
@@ -498,7 +539,7 @@ void build_lbvh_host(const float* pos, const int32_t* idx, const int32_t* prims,
             for (int a = 0; a < 3; a++) { bbox[6 * (size_t)x + a] = b.lo[a]; bbox[6 * (size_t)x + 3 + a] = b.hi[a]; }
         }
     }
-    std::vector<int32_t> defs{ploc ? n - 2 : n_int > 0 ? 0 : ~0}, next;
+    std::vector<int32_t> defs{sah ? sah_root : ploc ? n - 2 : n_int > 0 ? 0 : ~0}, next;
     out.tris.resize(n);
     int begin = 0, rec_begin = 0;
     while (!defs.empty()) {
@@ -542,7 +583,8 @@ int mpt_bvh_build_host_mode(const float* vertices, int32_t num_vertices, const i
                             const int32_t* prims, int32_t num_prims, int32_t mode, void* nodes, int64_t nodes_cap_bytes,
                             void* tris, int64_t tris_cap_bytes, int32_t* out_counts) {
     using namespace mpt;
-    if (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC) return api_fail(MPT_ERR_INVALID_ARGUMENT, "bvh: unknown build mode");
+    if (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC && mode != MPT_BUILD_SAH)
+        return api_fail(MPT_ERR_INVALID_ARGUMENT, "bvh: unknown build mode");
     if (!vertices || !indices) return api_fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
     if (num_vertices <= 0 || num_triangles <= 0 || nodes_cap_bytes < 0 || tris_cap_bytes < 0)
         return api_fail(MPT_ERR_INVALID_ARGUMENT, "bvh: bad size");

@@ -1368,7 +1368,8 @@ int mpt_rebuild_bvh(MptContext* c, MptRebuildInfo* info) { return mpt_rebuild_bv
 
 int mpt_rebuild_bvh_mode(MptContext* c, int32_t mode, MptRebuildInfo* info) {
     if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC) return fail(MPT_ERR_INVALID_ARGUMENT, "bvh: unknown build mode");
+    if (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC && mode != MPT_BUILD_SAH)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "bvh: unknown build mode");
     if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -1431,6 +1432,9 @@ int mpt_rebuild_bvh_mode(MptContext* c, int32_t mode, MptRebuildInfo* info) {
     }
     c->mirrors_stale = true;
     c->topology_stale = true;
+    if (mode == MPT_BUILD_SAH && std::getenv("MPT_SAH_STATS"))    // (the same aid: levels, and those without a grid-path node)
+        std::fprintf(stderr, "mpt sah: scene levels %d small-only %d, light levels %d small-only %d\n", ps.iterations,
+                     ps.tail_iterations, psl.iterations, psl.tail_iterations);
     if (mode == MPT_BUILD_PLOC && std::getenv("MPT_PLOC_STATS"))   // (a measuring aid: tools/rebuild_time.py)
         std::fprintf(stderr, "mpt ploc: scene iterations %d tail %d, light iterations %d tail %d\n", ps.iterations,
                      ps.tail_iterations, psl.iterations, psl.tail_iterations);

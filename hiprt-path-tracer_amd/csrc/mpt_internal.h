@@ -430,7 +430,8 @@ struct LbvhDevice {
     int n_nodes = 0, n_tris = 0, depth = 0;
     std::vector<int32_t> level_begin;
 };
-// mode: MPT_BUILD_LBVH (Karras' radix tree) or MPT_BUILD_PLOC (ploc.h); stats: optional, mode 1
+// mode: MPT_BUILD_LBVH (Karras' radix tree), MPT_BUILD_PLOC (ploc.h) or MPT_BUILD_SAH (sah.h);
+// stats: optional, mode 1 (mode 3: iterations = levels, tail_iterations = levels without a grid-path node)
 struct PlocStats {
     int iterations = 0, tail_iterations = 0;
 };
@@ -457,6 +458,37 @@ struct PlocScratch {
 hipError_t ploc_tree_device(int n, const float* pbox, const uint32_t* order, int32_t* left, int32_t* right, int32_t* first,
                             int32_t* last, float* nbox, uint32_t* order_out, const PlocScratch& B, hipStream_t st,
                             PlocStats* stats);
+// sah.hip (sah.h): the binned-SAH tree over n >= 2 sorted positions into left / right / first / last /
+// nbox (n - 1 nodes); ord[cur] holds the Morton order, the two buffers take turns per level and
+// *order_at names the one that holds the final order; *root: the root's reference.  Scratch from
+// the caller: per position its node's index (two), the scan's words (n + 1) and partial sums; per
+// list node (list_cap = n / 2 + 1, two lists) range and parent slot; per list node decision, split
+// position, B, CB and the child-count word; per grid-path slot (big_slots) encoded B, CB and bins.
+struct SahScratch {
+    int tail, big_slots, list_cap;
+    int32_t* nid[2];
+    int32_t* lfirst[2];
+    int32_t* llast[2];
+    int32_t* lpslot[2];
+    int32_t* dec;
+    int32_t* nmid;
+    float* nB;
+    double* nCB;
+    uint64_t* cw;
+    uint64_t* words;
+    uint64_t* partial;
+    uint32_t* gB;
+    uint64_t* gCB;
+    uint32_t* gbins;
+    int32_t* report;         // 2 words
+};
+struct SahStats {
+    int levels = 0, grid_levels = 0;
+};
+int sah_tail_from_env();     // MPT_SAH_TAIL (read at the call): 0 sends every node down the grid path
+hipError_t sah_tree_device(int n, const float* pbox, uint32_t* const ord[2], int cur, int32_t* left, int32_t* right, int32_t* first,
+                           int32_t* last, float* nbox, const SahScratch& B, hipStream_t st, int32_t* root, int* order_at,
+                           SahStats* stats);
 hipError_t launch_trace_raw(const DevScene& S, const float4* o, const float4* d, int n, bool any, float4* out_hit,
                             uint8_t* out_occ, int32_t* fetch_ctr, uint32_t* spill, int grid, hipStream_t st);
 

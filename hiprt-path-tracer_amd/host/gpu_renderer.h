@@ -130,8 +130,9 @@ public:
     // rebuild_bvh (no counterpart in the reference): every context rebuilds its BVHs on its GPU
     // from the positions it holds (mpt_rebuild_bvh_mode), e.g. once update_vertices reports a large
     // area_ratio.  The accumulation continues: traversal results do not depend on the tree.
-    // info (optional): the first context's report.  mode: MPT_BUILD_LBVH, or MPT_BUILD_PLOC for a
-    // better tree from a slower build.
+    // info (optional): the first context's report.  mode: MPT_BUILD_LBVH, MPT_BUILD_PLOC for a
+    // better tree from a slower build, or MPT_BUILD_SAH for the host builder's tree quality from the
+    // slowest of the three.
     void rebuild_bvh(MptRebuildInfo* info = nullptr, int32_t mode = MPT_BUILD_LBVH);
     const std::vector<MptMaterial>& get_original_materials() const { return m_original_materials; }
     const std::vector<MptMaterial>& get_current_materials() const { return m_current_materials; }

@@ -309,7 +309,7 @@ def bvh_refit_host(build_vertices, indices, new_vertices=None):
 
 def bvh_build_host(vertices, indices, prims=None, mode=abi.BUILD_LBVH):
     """mpt_bvh_build_host_mode, no GPU: the BVH8 a rebuild makes (csrc/lbvh.h; mode abi.BUILD_PLOC:
-    with the binary tree of csrc/ploc.h) over vertices ([V, 3] float32) and indices ([T, 3] int32),
+    with the binary tree of csrc/ploc.h; mode abi.BUILD_SAH: with the binned-SAH tree of csrc/sah.h) over vertices ([V, 3] float32) and indices ([T, 3] int32),
     over all triangles or over the scene primitives listed in prims.  Returns (nodes, tris, levels)
     as bvh_refit_host does: the bytes GPURenderer.get_bvh returns after rebuild_bvh(mode=mode) (the
     records' flag lanes are 0 here)."""
@@ -362,8 +362,9 @@ class GPURenderer:
 
     def rebuild_bvh(self, info=False, mode=abi.BUILD_LBVH):
         """mpt_rebuild_bvh_mode: both BVHs rebuilt on the GPU from the positions on the device, as
-        an LBVH (abi.BUILD_LBVH) or by PLOC (abi.BUILD_PLOC: a better tree, a slower build).  No
-        frame reset is needed.  info=True returns the abi.RebuildInfo, else None."""
+        an LBVH (abi.BUILD_LBVH), by PLOC (abi.BUILD_PLOC: a better tree, a slower build) or top down
+        with binned SAH (abi.BUILD_SAH: the host builder's tree quality, the slowest of the three).
+        No frame reset is needed.  info=True returns the abi.RebuildInfo, else None."""
         ri = abi.RebuildInfo() if info else None
         _check(lib().mpt_rebuild_bvh_mode(self.h, int(mode), C.byref(ri) if info else None))
         return ri

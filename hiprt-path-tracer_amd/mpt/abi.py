@@ -460,7 +460,7 @@ class RefitInfo(C.Structure):
                 ("area_ratio", f32), ("light_area_ratio", f32)]
 
 
-BUILD_LBVH, BUILD_PLOC = 0, 1   # MPT_BUILD_*: the build modes of mpt_rebuild_bvh_mode
+BUILD_LBVH, BUILD_PLOC, BUILD_SAH = 0, 1, 3   # MPT_BUILD_*: the build modes of mpt_rebuild_bvh_mode (2 is none)
 
 
 class RebuildInfo(C.Structure):

@@ -15,8 +15,8 @@
  *                                    vertices with a GPU refit of both BVH8s
  *   mpt_rebuild_bvh               <- (no counterpart: HIPRT rebuilds with the geometry) both BVH8s
  *   mpt_rebuild_bvh_mode             rebuilt on the GPU from the positions on the device: an LBVH
- *                                    (mode 0, the default) or PLOC (mode 1; the reference builds with
- *                                    hiprtBuildFlagBitPreferHighQualityBuild)
+ *                                    (mode 0, the default), PLOC (mode 1) or binned SAH (mode 3; the
+ *                                    reference builds with hiprtBuildFlagBitPreferHighQualityBuild)
  *   mpt_set_envmap                <- GPURenderer::set_envmap (GPURenderer.h:222, .cpp:1136-1174)
  *   mpt_set_luts                  <- GPURenderer::setup_brdfs_data (GPURenderer.h:76, .cpp:88-175)
  *   mpt_resize                    <- GPURenderer::resize (GPURenderer.h:172)
@@ -632,13 +632,21 @@ int mpt_rebuild_bvh(MptContext* ctx, MptRebuildInfo* info_or_NULL);
  * builds).  MPT_BUILD_PLOC: the binary tree comes from parallel locally-ordered clustering over the
  * same Morton order instead (csrc/ploc.h: radius 8, mutual nearest neighbours by the fp32 area of
  * the union merge, iterated until one cluster is left); keys, sort, collapse, slots, layout, flag
- * lanes and refit are the same code.  A lower-area tree for more build time. */
+ * lanes and refit are the same code.  A lower-area tree for more build time.
+ * MPT_BUILD_SAH: the binary tree comes from a top-down build with 32 bins per axis over the same
+ * Morton order (csrc/sah.h: the algorithm of mpt_upload_scene's host builder, level by level, with a
+ * stable partition); everything else is again the same code.  Its value is 3: 2 is not a mode and
+ * stays refused with MPT_ERR_INVALID_ARGUMENT, as it always was. */
 #define MPT_BUILD_LBVH 0
 #define MPT_BUILD_PLOC 1
+#define MPT_BUILD_SAH 3
 /* mpt_rebuild_bvh with a build mode for both trees; mode 0 is mpt_rebuild_bvh, byte for byte.  An
  * unknown mode returns MPT_ERR_INVALID_ARGUMENT and changes nothing.  Every other rule of
  * mpt_rebuild_bvh holds as stated there.  MPT_PLOC_TAIL=0 in the environment (read at the call)
- * keeps mode 1 from finishing its last 1024 clusters in one workgroup: the same bytes, slower. */
+ * keeps mode 1 from finishing its last 1024 clusters in one workgroup: the same bytes, slower.
+ * MPT_SAH_TAIL=0 sends every node of mode 3 down the path of nodes above 1024 triangles (bins in
+ * global memory) instead of one wave per node: the same bytes.  MPT_SAH_DEPTH=d (both entry points)
+ * lowers the depth below which mode 3 splits by count only, 40: a test hook. */
 int mpt_rebuild_bvh_mode(MptContext* ctx, int32_t mode, MptRebuildInfo* info_or_NULL);
 /* No device needed: the host loop of the same definition over the list prims (NULL: all
  * num_triangles primitives in order; else num_prims > 0 scene primitive indices) -- the bytes

@@ -22,8 +22,11 @@ after the timed repeats.  Writes one JSON document (--out) and prints it.
 to the LBVH's inside every repeat, a fourth context `rebuilt_ploc` joins the render columns, and
 the iteration counts of both trees (and how many ran in the single-workgroup tail) are taken from
 the library's MPT_PLOC_STATS line of one extra call.  With --variant rebuild the calls use the mode.
---rebuild-only times just the rebuilds (of --mode 0, and of mode 1 when given): the run to make
-with --pkg at a commit that has mpt_rebuild_bvh only, to show that mode 0 has not moved."""
+--mode 3 adds the binned-SAH build mode (MPT_BUILD_SAH) on top of --mode 1: its rebuild is timed
+next to the LBVH's and PLOC's inside every repeat, a fifth context `rebuilt_sah` joins the render
+columns, and its level counts come from the library's MPT_SAH_STATS line.
+--rebuild-only times just the rebuilds (of --mode 0, and of the modes --mode adds): the run to make
+with --pkg at a commit that lacks the newest mode, to show that the older modes have not moved."""
 import argparse
 import copy
 import ctypes as C
@@ -50,7 +53,7 @@ def main():
     ap.add_argument("--sets", default="identity,jitter_1pct", help="vertex sets of the render columns (also: jitter_x10)")
     ap.add_argument("--upload-only", action="store_true")
     ap.add_argument("--rebuild-only", action="store_true")
-    ap.add_argument("--mode", type=int, default=0, help="1: also the PLOC build mode")
+    ap.add_argument("--mode", type=int, default=0, help="1: also the PLOC build mode; 3: PLOC and the binned-SAH mode")
     ap.add_argument("--variant", default=None)
     ap.add_argument("--pkg", default=os.path.join(ROOT, "hiprt-path-tracer_amd"))
     ap.add_argument("--out", default=None)
@@ -119,26 +122,34 @@ def main():
                 r.rebuild_bvh(**({"mode": a.mode} if a.mode else {}))
         return
 
-    def ploc_stats(r):
-        """The library's report of one mode-1 rebuild (a line on stderr under MPT_PLOC_STATS)."""
+    def ploc_stats(r, mode=1):
+        """The library's report of one mode-1 (mode-3) rebuild (a line on stderr under MPT_PLOC_STATS,
+        MPT_SAH_STATS)."""
         import re
+        var = "MPT_SAH_STATS" if mode == 3 else "MPT_PLOC_STATS"
         import tempfile
         with tempfile.TemporaryFile() as tmp:
             sys.stderr.flush()
             saved = os.dup(2)
             os.dup2(tmp.fileno(), 2)
-            os.environ["MPT_PLOC_STATS"] = "1"
+            os.environ[var] = "1"
             try:
-                r.rebuild_bvh(mode=1)
+                r.rebuild_bvh(mode=mode)
             finally:
-                del os.environ["MPT_PLOC_STATS"]
+                del os.environ[var]
                 os.dup2(saved, 2)
                 os.close(saved)
             tmp.seek(0)
-            m = re.search(r"scene iterations (\d+) tail (\d+), light iterations (\d+) tail (\d+)", tmp.read().decode())
+            text = tmp.read().decode()
+            if mode == 3:
+                m = re.search(r"scene levels (\d+) small-only (\d+), light levels (\d+) small-only (\d+)", text)
+                return dict(zip(("levels", "small_only_levels", "light_levels", "light_small_only_levels"), map(int, m.groups())))
+            m = re.search(r"scene iterations (\d+) tail (\d+), light iterations (\d+) tail (\d+)", text)
         return dict(zip(("iterations", "tail_iterations", "light_iterations", "light_tail_iterations"), map(int, m.groups())))
 
-    modes = (0, 1) if a.mode else (0,)
+    modes = {0: (0,), 1: (0, 1), 3: (0, 1, 3)}[a.mode]
+    KEY = {0: "rebuild", 1: "rebuild_ploc", 3: "rebuild_sah"}
+    sah = a.mode == 3
     if a.rebuild_only:
         with mpt.GPURenderer(0, stream=stream.cuda_stream) as r:
             r.set_scene(sd0)
@@ -152,10 +163,12 @@ def main():
                     ts[m][0].append(w)
                     ts[m][1].append(g)
             for m in modes:
-                key = "rebuild_ploc" if m else "rebuild"
+                key = KEY[m]
                 out[key + "_wall_ms"], out[key + "_gpu_ms"] = stats(ts[m][0]), stats(ts[m][1])
             if a.mode:
                 out["ploc"] = ploc_stats(r)
+            if sah:
+                out["sah"] = ploc_stats(r, 3)
         return finish(a, out)
 
     W, H = 1920, 1080
@@ -196,10 +209,11 @@ def main():
             sets[name] = v10
         else:
             sets[name] = {"identity": v0, "jitter_1pct": v1}[name]
-    cols = ("rebuilt_gpu", "fresh_upload", "refitted") + (("rebuilt_ploc",) if a.mode else ())
+    cols = ("rebuilt_gpu", "fresh_upload", "refitted") + (("rebuilt_ploc",) if a.mode else ()) + (("rebuilt_sah",) if sah else ())
     with mpt.GPURenderer(0, stream=stream.cuda_stream) as rb, mpt.GPURenderer(0, stream=stream.cuda_stream) as rf, \
-            mpt.GPURenderer(0, stream=stream.cuda_stream) as rr, mpt.GPURenderer(0, stream=stream.cuda_stream) as rp:
-        ctx = dict(zip(cols, (rb, rf, rr, rp)))
+            mpt.GPURenderer(0, stream=stream.cuda_stream) as rr, mpt.GPURenderer(0, stream=stream.cuda_stream) as rp, \
+            mpt.GPURenderer(0, stream=stream.cuda_stream) as rs:
+        ctx = dict(zip(cols, (rb, rf, rr, rp, rs)))
         for r in ctx.values():
             r.set_scene(sd0)
             r.set_luts(luts)
@@ -211,6 +225,10 @@ def main():
         if a.mode:
             rp.update_vertices(v1)
             rebuild_ms(rp, 1)
+        t_wall_s, t_gpu_s, info_s = [], [], None
+        if sah:
+            rs.update_vertices(v1)
+            rebuild_ms(rs, 3)
         t_wall, t_gpu, t_upload = [], [], []
         t_render = {name: {c: [] for c in cols} for name in sets}
         info = None
@@ -224,6 +242,11 @@ def main():
                 w, g, info_p = rebuild_ms(rp, 1)
                 t_wall_p.append(w)
                 t_gpu_p.append(g)
+            if sah:
+                rs.update_vertices(v1)
+                w, g, info_s = rebuild_ms(rs, 3)
+                t_wall_s.append(w)
+                t_gpu_s.append(g)
             t_upload.append(upload_ms(rf, with_vertices(v1)))
             for name, v in sets.items():
                 rb.update_vertices(v)
@@ -231,6 +254,9 @@ def main():
                 if a.mode:
                     rp.update_vertices(v)
                     rp.rebuild_bvh(mode=1)
+                if sah:
+                    rs.update_vertices(v)
+                    rs.rebuild_bvh(mode=3)
                 upload_ms(rf, with_vertices(v))
                 rr.update_vertices(v)
                 for c in cols:
@@ -249,6 +275,12 @@ def main():
                                light_levels=info_p.light_levels)
             out["rebuild_ploc_wall_ms"] = stats(t_wall_p)
             out["rebuild_ploc_gpu_ms"] = stats(t_gpu_p)
+        if sah:
+            rs.update_vertices(v1)
+            out["sah"] = dict(ploc_stats(rs, 3), nodes=info_s.nodes, tree_levels=info_s.levels, light_nodes=info_s.light_nodes,
+                              light_tree_levels=info_s.light_levels)
+            out["rebuild_sah_wall_ms"] = stats(t_wall_s)
+            out["rebuild_sah_gpu_ms"] = stats(t_gpu_s)
         out["render"] = {"width": W, "height": H, "samples": a.samples, "batch": a.batch, "unit": "wall ms per sample"}
         for name, v in sets.items():
             rb.update_vertices(v)
@@ -256,6 +288,9 @@ def main():
             if a.mode:
                 rp.update_vertices(v)
                 rp.rebuild_bvh(mode=1)
+            if sah:
+                rs.update_vertices(v)
+                rs.rebuild_bvh(mode=3)
             upload_ms(rf, with_vertices(v))
             ri = rr.update_vertices(v, info=True)
             out["render"][name] = {c: dict(stats(t_render[name][c]), **per_ray(ctx[c])) for c in cols}
