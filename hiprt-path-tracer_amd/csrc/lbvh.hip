@@ -17,7 +17,8 @@
 //   k_collapse_count / k_collapse_emit   per breadth-first level: one thread per node chooses its
 //                     children and slots, the counts are scanned in node order, the emit writes the
 //                     nodes' topology bytes, the next level's list and the records' w lanes
-//   k_flag_scatter    the old records' flag lanes into a per-primitive scratch (gathered by the emit)
+//   k_flag_scatter    the old records' flag lanes into a per-primitive scratch (gathered by the emit;
+//                     not run when the caller brings the words: mpt_upload_scene_mode, upload.hip)
 // No kernel waits on, or depends on seeing, what another workgroup writes in the same launch.
 #include <hip/hip_runtime.h>
 
@@ -323,7 +324,7 @@ void free_lbvh(LbvhDevice& o) {
 
 hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, const int32_t* idx, const float* pos, float pad,
                              const TriRec* old_tris, int n_old, float* tbox, LbvhDevice& out, hipStream_t st, int mode,
-                             PlocStats* stats) {
+                             PlocStats* stats, const uint32_t* ready_flags) {
     out = LbvhDevice{};
     if (n <= 0 || (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC && mode != MPT_BUILD_SAH)) return hipErrorInvalidValue;
     const bool ploc = mode == MPT_BUILD_PLOC && n > 1;
@@ -350,7 +351,8 @@ hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, c
     float* bbox = S.get<float>(6 * (size_t)n_int);
     int32_t* defs[2] = {S.get<int32_t>(cap), S.get<int32_t>(cap)};
     int32_t* slots = S.get<int32_t>(8 * (size_t)cap);
-    uint32_t* flags = S.get<uint32_t>(2 * (size_t)n_scene_prims);
+    uint32_t* scattered = ready_flags ? nullptr : S.get<uint32_t>(2 * (size_t)n_scene_prims);
+    const uint32_t* flags = ready_flags ? ready_flags : scattered;
     Node8* nodes = S.get<Node8>(cap);
     PlocScratch PS{};
     if (ploc) {
@@ -391,10 +393,12 @@ hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, c
     LB(S.err);
     LB(hipMalloc(&out.tris, (size_t)n * sizeof(TriRec)));
 
-    // the flag lanes of the old records, per scene primitive
-    LB(hipMemsetAsync(flags, 0, 2 * (size_t)n_scene_prims * sizeof(uint32_t), st));
-    if (old_tris && n_old > 0)
-        hipLaunchKernelGGL(k_flag_scatter, dim3(blocks(n_old)), dim3(BLK), 0, st, old_tris, n_old, n_scene_prims, flags);
+    // the flag lanes per scene primitive: the caller's words, or those of the old records
+    if (scattered) {
+        LB(hipMemsetAsync(scattered, 0, 2 * (size_t)n_scene_prims * sizeof(uint32_t), st));
+        if (old_tris && n_old > 0)
+            hipLaunchKernelGGL(k_flag_scatter, dim3(blocks(n_old)), dim3(BLK), 0, st, old_tris, n_old, n_scene_prims, scattered);
+    }
     // keys
     hipLaunchKernelGGL(k_prim_boxes, dim3(blocks(n)), dim3(BLK), 0, st, d_prims, n, idx, pos, pad, pbox, bpart + 6);
     hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(BLK), 0, st, bpart + 6, (int)blocks(n), bpart);

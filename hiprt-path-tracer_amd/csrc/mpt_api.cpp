@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +22,7 @@
 #include "mpt.h"
 #include "mpt_internal.h"
 #include "refit.h"
+#include "upload.h"
 
 using namespace mpt;
 
@@ -648,14 +650,22 @@ int refresh_mirrors(MptContext* c) {
 // Alpha-test flag of every triangle record (TriRec::pad0): the filter function's test
 // (FilterFunction.h:19-48) can only reject a hit when alpha_opacity < 1 or the base
 // colour texture has a texel with alpha < 255; all other triangles skip it for free.
+bool material_alpha_flag(const MptContext* c, const MptMaterial& m) {
+    int bt = m.base_color_texture_index;
+    bool tex_alpha = bt >= 0 && bt < (int)c->h_tex_alpha.size() && c->h_tex_alpha[bt];
+    return m.alpha_opacity < 1.0f || tex_alpha;
+}
+
+// The light-hit BVH's predicate (build_light_bvh_impl, below): the material's emission can be non-black.
+bool material_lit(const MptMaterial& m) {
+    const float k = m.emission_strength;
+    return m.emission_texture_index != MPT_NO_TEXTURE || m.emission.r * k > 0.0f || m.emission.g * k > 0.0f ||
+           m.emission.b * k > 0.0f;
+}
+
 int upload_alpha_flags(MptContext* c) {
     std::vector<uint8_t> mflag(c->h_mats.size());
-    for (size_t i = 0; i < c->h_mats.size(); i++) {
-        const MptMaterial& m = c->h_mats[i];
-        int bt = m.base_color_texture_index;
-        bool tex_alpha = bt >= 0 && bt < (int)c->h_tex_alpha.size() && c->h_tex_alpha[bt];
-        mflag[i] = (m.alpha_opacity < 1.0f || tex_alpha) ? 1 : 0;
-    }
+    for (size_t i = 0; i < c->h_mats.size(); i++) mflag[i] = material_alpha_flag(c, c->h_mats[i]) ? 1 : 0;
     bool changed = false;
     for (TriRec& tr : c->bvh.tris) {
         int32_t prim;
@@ -688,13 +698,8 @@ int upload_alpha_flags(MptContext* c) {
 static int build_light_bvh_impl(MptContext* c, hipError_t& herr) {
     std::vector<uint8_t> lit(c->h_mats.size()), aflag(c->h_mats.size());
     for (size_t i = 0; i < c->h_mats.size(); i++) {
-        const MptMaterial& m = c->h_mats[i];
-        const float k = m.emission_strength;
-        lit[i] = (m.emission_texture_index != MPT_NO_TEXTURE || m.emission.r * k > 0.0f || m.emission.g * k > 0.0f ||
-                  m.emission.b * k > 0.0f) ? 1 : 0;
-        int bt = m.base_color_texture_index;
-        bool tex_alpha = bt >= 0 && bt < (int)c->h_tex_alpha.size() && c->h_tex_alpha[bt];
-        aflag[i] = (m.alpha_opacity < 1.0f || tex_alpha) ? 1 : 0;
+        lit[i] = material_lit(c->h_mats[i]) ? 1 : 0;
+        aflag[i] = material_alpha_flag(c, c->h_mats[i]) ? 1 : 0;
     }
     std::vector<int32_t> prims;
     for (size_t t = 0; t < c->h_mat_idx.size(); t++)
@@ -866,13 +871,15 @@ int ensure_restir(MptContext* c, const MptFrame* f) {
     return MPT_OK;
 }
 
-int resolve_materials(MptContext* c) {
+// The materials' resolution, their classes (t: the host copy of mat_tex) and what the host keeps
+// of them; touches no tree.
+int resolve_material_tables(MptContext* c, std::vector<int32_t>& t) {
     size_t n = c->h_mats.size();
     HIPCHK(c->mats_res.alloc(n));
     HIPCHK(c->mat_tex.alloc(n));
     HIPCHK(c->em_tab.alloc(5 * std::max<size_t>(c->emissive.n, 1)));
     HIPCHK(launch_resolve_materials(dev_scene(c), c->mats_res.p, c->mat_tex.p, (int)n, c->em_tab.p, c->stream));
-    std::vector<int32_t> t(n);
+    t.assign(n, 0);
     HIPCHK(hipMemcpyAsync(t.data(), c->mat_tex.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->any_tex = c->any_glass = false;
@@ -885,13 +892,23 @@ int resolve_materials(MptContext* c) {
     size_t n_tex_tris = 0;
     for (int32_t mi : c->h_mat_idx) n_tex_tris += (mi >= 0 && (size_t)mi < n && (t[mi] & MT_TEXTURED)) ? 1 : 0;
     c->tex_tri_frac = c->h_mat_idx.empty() ? 0.0 : (double)n_tex_tris / (double)c->h_mat_idx.size();
+    return MPT_OK;
+}
+
+// the mask of a material's class (mat_tex) in a triangle record (TriRec::pad1)
+int32_t class_keep_mask(const MptContext* c) { return 0x7f & ~(c->shade_texmetal ? 0 : MT_TEXMETAL); }
+
+int resolve_materials(MptContext* c) {
+    std::vector<int32_t> t;
+    const int rt = resolve_material_tables(c, t);
+    if (rt != MPT_OK) return rt;
     // each triangle's material class in its BVH record (TriRec::pad1): the path traversal
     // reports it with the hit (DevPaths::hit_cls), so k_split needs no material lookups
     bool changed = false;
     for (TriRec& tr : c->bvh.tris) {
         int32_t prim;
         std::memcpy(&prim, &tr.prim_bits, 4);
-        const int32_t keep = 0x7f & ~(c->shade_texmetal ? 0 : MT_TEXMETAL);
+        const int32_t keep = class_keep_mask(c);
         const uint32_t cls = (prim >= 0 && (size_t)prim < c->h_mat_idx.size()) ? (uint32_t)(t[c->h_mat_idx[prim]] & keep) : 0u;
         uint32_t old;
         std::memcpy(&old, &tr.pad1, 4);
@@ -1152,8 +1169,8 @@ int mpt_destroy(MptContext* c) {
     return MPT_OK;
 }
 
-int mpt_upload_scene(MptContext* c, const MptScene* s) {
-    if (!c || !s) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+// The argument checks of a scene upload (mpt_upload_scene, mpt_upload_scene_mode).
+static int check_scene(const MptScene* s) {
     if (s->num_triangles <= 0 || s->num_vertices <= 0 || !s->triangle_indices || !s->vertices || !s->material_indices ||
         !s->materials || s->num_materials <= 0)
         return fail(MPT_ERR_INVALID_ARGUMENT, "scene has no geometry or materials");
@@ -1166,12 +1183,13 @@ int mpt_upload_scene(MptContext* c, const MptScene* s) {
     for (int i = 0; i < s->num_emissive_triangles; i++)
         if (s->emissive_triangle_indices[i] < 0 || s->emissive_triangle_indices[i] >= s->num_triangles)
             return fail(MPT_ERR_INVALID_ARGUMENT, "emissive triangle index out of range");
-    HIPCHK(hipSetDevice(c->device));
-    const int stack_cap = build_scene_bvh8(s->vertices, s->triangle_indices, s->num_triangles, c->bvh, MAX_STACK);
+    return MPT_OK;
+}
+
+// What a scene upload keeps on the host besides its trees: the box pad, the vertices in use, the
+// copies of indices and positions; no light set yet.
+static void take_scene_mirrors(MptContext* c, const MptScene* s) {
     c->box_pad = scene_box_pad(s->vertices, s->num_triangles, s->triangle_indices);
-    c->area0 = node_box_area_sum(c->bvh.node_box.data(), c->bvh.nodes.size());
-    c->mirrors_stale = false;
-    c->topology_stale = false;
     c->h_vert_used.assign((size_t)s->num_vertices, 0);
     for (size_t k = 0; k < 3 * (size_t)s->num_triangles; k++) c->h_vert_used[s->triangle_indices[k]] = 1;
     c->h_idx.assign(s->triangle_indices, s->triangle_indices + 3 * (size_t)s->num_triangles);
@@ -1179,10 +1197,40 @@ int mpt_upload_scene(MptContext* c, const MptScene* s) {
     c->h_light_prims.clear();
     c->nodes_light.release();
     c->tris_light.release();
+}
+
+static int upload_scene_arrays(MptContext* c, const MptScene* s);
+
+int mpt_upload_scene(MptContext* c, const MptScene* s) {
+    if (!c || !s) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    const int rc = check_scene(s);
+    if (rc != MPT_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const int stack_cap = build_scene_bvh8(s->vertices, s->triangle_indices, s->num_triangles, c->bvh, MAX_STACK);
+    c->area0 = node_box_area_sum(c->bvh.node_box.data(), c->bvh.nodes.size());
+    c->mirrors_stale = false;
+    c->topology_stale = false;
+    take_scene_mirrors(c, s);
     if (2 * c->bvh.depth + 2 > stack_cap) return fail(MPT_ERR_UNSUPPORTED, "BVH8 deeper than the traversal stack");
     hipStream_t st = c->stream;
     HIPCHK(c->nodes.upload(c->bvh.nodes.data(), c->bvh.nodes.size(), st));
     HIPCHK(c->tris.upload(c->bvh.tris.data(), c->bvh.tris.size(), st));
+    int rr = upload_scene_arrays(c, s);
+    if (rr != MPT_OK) return rr;
+    rr = upload_alpha_flags(c);
+    if (rr != MPT_OK) return rr;
+    rr = build_light_bvh(c);
+    if (rr != MPT_OK) return rr;
+    rr = resolve_materials(c);
+    if (rr != MPT_OK) return rr;
+    c->has_scene = true;
+    return MPT_OK;
+}
+
+// Every device array of a scene but the trees, the per-triangle attributes, and the host copies
+// of the materials, material indices and the textures' alpha; the stream is synchronised.
+static int upload_scene_arrays(MptContext* c, const MptScene* s) {
+    hipStream_t st = c->stream;
     HIPCHK(c->idx.upload(s->triangle_indices, 3 * (size_t)s->num_triangles, st));
     HIPCHK(c->pos.upload(s->vertices, 3 * (size_t)s->num_vertices, st));
     std::vector<float> zeros3, zeros2;
@@ -1230,13 +1278,6 @@ int mpt_upload_scene(MptContext* c, const MptScene* s) {
         c->h_tex_alpha.clear();
         HIPCHK(hipStreamSynchronize(st));
     }
-    int rr = upload_alpha_flags(c);
-    if (rr != MPT_OK) return rr;
-    rr = build_light_bvh(c);
-    if (rr != MPT_OK) return rr;
-    rr = resolve_materials(c);
-    if (rr != MPT_OK) return rr;
-    c->has_scene = true;
     return MPT_OK;
 }
 
@@ -1364,6 +1405,18 @@ int mpt_update_vertices(MptContext* c, const float* vertices, const float* verte
     return MPT_OK;
 }
 
+// A tree built on the device takes the place of the context's: the buffers change hands, the host
+// copy keeps the levels (its nodes and records follow with refresh_mirrors, topology_stale).
+static void swap_in(DBuf<Node8>& dn, DBuf<TriRec>& dt, DBuf<float>& db, BVH8& h, LbvhDevice& t) {
+    dn.release(); dt.release(); db.release();
+    dn.p = t.nodes; dn.n = (size_t)t.n_nodes;
+    dt.p = t.tris; dt.n = (size_t)t.n_tris;
+    db.p = t.nbox; db.n = 6 * (size_t)t.n_nodes;
+    t.nodes = nullptr; t.tris = nullptr; t.nbox = nullptr;
+    h.level_begin = t.level_begin;
+    h.depth = t.depth;
+}
+
 int mpt_rebuild_bvh(MptContext* c, MptRebuildInfo* info) { return mpt_rebuild_bvh_mode(c, MPT_BUILD_LBVH, info); }
 
 int mpt_rebuild_bvh_mode(MptContext* c, int32_t mode, MptRebuildInfo* info) {
@@ -1413,15 +1466,6 @@ int mpt_rebuild_bvh_mode(MptContext* c, int32_t mode, MptRebuildInfo* info) {
         c->has_scene = false;   // the caller uploads again
         return fail(MPT_ERR_HIP, std::string("mpt_rebuild_bvh: ") + hipGetErrorString(e));
     }
-    auto swap_in = [](DBuf<Node8>& dn, DBuf<TriRec>& dt, DBuf<float>& db, BVH8& h, LbvhDevice& t) {
-        dn.release(); dt.release(); db.release();
-        dn.p = t.nodes; dn.n = (size_t)t.n_nodes;
-        dt.p = t.tris; dt.n = (size_t)t.n_tris;
-        db.p = t.nbox; db.n = 6 * (size_t)t.n_nodes;
-        t.nodes = nullptr; t.tris = nullptr; t.nbox = nullptr;
-        h.level_begin = t.level_begin;
-        h.depth = t.depth;
-    };
     swap_in(c->nodes, c->tris, c->nbox, c->bvh, T);
     c->area0 = node_box_area_sum(hb.data(), (size_t)T.n_nodes);
     if (light_fits) {
@@ -1444,6 +1488,151 @@ int mpt_rebuild_bvh_mode(MptContext* c, int32_t mode, MptRebuildInfo* info) {
         if (light_fits) { r.light_rebuilt = 1; r.light_nodes = TL.n_nodes; r.light_records = TL.n_tris; r.light_levels = TL.depth; }
         *info = r;
     }
+    return MPT_OK;
+}
+
+// A scene upload without a tree built on the host (DESIGN.md §2 "Uploads with a build mode"): the
+// arrays as mpt_upload_scene uploads them, the materials resolved, the records' flag words and the
+// light set made per primitive on the device (upload.hip), then both trees by build_lbvh_device.
+int mpt_upload_scene_mode(MptContext* c, const MptScene* s, int32_t mode, MptRebuildInfo* info) {
+    if (!c || !s) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (mode != MPT_BUILD_LBVH && mode != MPT_BUILD_PLOC && mode != MPT_BUILD_SAH)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "bvh: unknown build mode");
+    // wall-clock per phase (MPT_UPLOAD_STATS in the environment prints them: tools/upload_time.py)
+    enum { PH_CHECK, PH_MIRRORS, PH_ARRAYS, PH_MATERIALS, PH_BUILD, PH_SELECT, PH_BUILD_LIGHT, PH_DOWNLOAD, PH_COUNT };
+    double ms[PH_COUNT] = {};
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](int k) {
+        const auto t1 = std::chrono::steady_clock::now();
+        ms[k] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+    };
+    const int rc = check_scene(s);
+    if (rc != MPT_OK) return rc;
+    lap(PH_CHECK);
+    c->has_scene = false;   // from here on a failure leaves the context without a scene
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(drain(c));
+    hipStream_t st = c->stream;
+    take_scene_mirrors(c, s);
+    lap(PH_MIRRORS);
+    int rr = upload_scene_arrays(c, s);
+    if (rr != MPT_OK) return rr;
+    lap(PH_ARRAYS);
+    // materials first: the build stamps their classes into the records
+    std::vector<int32_t> mat_tex;
+    rr = resolve_material_tables(c, mat_tex);
+    if (rr != MPT_OK) return rr;
+    const int n = s->num_triangles, n_mats = s->num_materials;
+    std::vector<uint32_t> mf((size_t)n_mats);
+    bool any_lit = false;
+    for (int i = 0; i < n_mats; i++) {
+        const bool lit = material_lit(c->h_mats[i]);
+        mf[i] = (material_alpha_flag(c, c->h_mats[i]) ? MF_ALPHA : 0u) | (lit ? MF_LIT : 0u);
+        any_lit |= lit;
+    }
+    int stack_cap = MAX_STACK;   // as build_scene_bvh8
+    if (const char* ev = std::getenv("MPT_BVH_MAX_STACK")) stack_cap = std::max(4, std::min(MAX_STACK, std::atoi(ev)));
+    const int light_cap = std::min(MAX_STACK, c->light_bvh_max_stack);
+    DBuf<uint32_t> d_mf, d_flags;
+    DBuf<uint64_t> d_words, d_partial;
+    DBuf<int32_t> d_light;
+    LbvhDevice T, TL;
+    PlocStats ps, psl;
+    hipError_t e = d_mf.upload(mf.data(), mf.size(), st);
+    if (e == hipSuccess) e = d_flags.alloc(2 * (size_t)n);
+    if (e == hipSuccess) e = c->tbox.alloc(6 * (size_t)n);
+    if (e == hipSuccess) e = launch_prim_flags(c->mat_idx.p, n, d_mf.p, c->mat_tex.p, n_mats, class_keep_mask(c), d_flags.p, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    lap(PH_MATERIALS);
+    if (e == hipSuccess)
+        e = build_lbvh_device(nullptr, n, n, c->idx.p, c->pos.p, c->box_pad, nullptr, 0, c->tbox.p, T, st, mode, &ps, d_flags.p);
+    if (e == hipSuccess && 2 * T.depth + 2 > stack_cap) {
+        free_lbvh(T);
+        return fail(MPT_ERR_UNSUPPORTED, "BVH8 deeper than the traversal stack");
+    }
+    lap(PH_BUILD);
+    // the light set: mark, scan, scatter -- ascending by primitive, the list build_light_bvh_impl makes
+    int n_light = 0;
+    if (e == hipSuccess && any_lit) {
+        const int nb = (n + 255) / 256;   // scan_u64's workgroups
+        uint64_t total = 0;
+        e = d_words.alloc((size_t)n);
+        if (e == hipSuccess) e = d_partial.alloc((size_t)nb + 1);
+        if (e == hipSuccess) e = launch_light_mark(c->mat_idx.p, n, d_mf.p, n_mats, d_words.p, st);
+        if (e == hipSuccess) e = scan_u64(d_words.p, n, d_partial.p, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, d_partial.p + nb, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess && total > (uint64_t)n) e = hipErrorUnknown;
+        if (e == hipSuccess && total > 0) {
+            n_light = (int)total;
+            c->h_light_prims.assign((size_t)n_light, 0);
+            e = d_light.alloc((size_t)n_light);
+            if (e == hipSuccess) e = hipMemsetAsync(d_light.p, 0, (size_t)n_light * sizeof(int32_t), st);
+            if (e == hipSuccess) e = launch_light_scatter(c->mat_idx.p, n, d_mf.p, n_mats, d_words.p, d_light.p, n_light, st);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(c->h_light_prims.data(), d_light.p, (size_t)n_light * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+        }
+    }
+    lap(PH_SELECT);
+    // the light-hit tree: the same alpha flags, the class lane 0 as build_light_bvh_impl leaves it
+    c->light_bvh_ok = true;
+    if (e == hipSuccess && n_light > 0) {
+        hipError_t el = launch_prim_flags(c->mat_idx.p, n, d_mf.p, c->mat_tex.p, n_mats, 0, d_flags.p, st);
+        if (el == hipSuccess)
+            el = build_lbvh_device(d_light.p, n_light, n, c->idx.p, c->pos.p, c->box_pad, nullptr, 0, c->tbox.p, TL, st, mode, &psl,
+                                   d_flags.p);
+        if (el == hipErrorOutOfMemory) {   // build_light_bvh's rule: an optimisation lost, not the call
+            (void)hipGetLastError();
+            c->h_light_prims.clear();
+            c->light_bvh_ok = false;
+            e = hipStreamSynchronize(st);
+        } else if (el != hipSuccess) {
+            e = el;
+        } else if (2 * TL.depth + 2 > light_cap) {
+            // too deep for the traversal stack: dropped as build_light_bvh_impl drops it -- no list,
+            // and light-hit queries take the (exact) whole-scene closest-hit path
+            free_lbvh(TL);
+            c->h_light_prims.clear();
+            c->light_bvh_ok = false;
+        }
+    }
+    lap(PH_BUILD_LIGHT);
+    std::vector<float> hb, hbl;
+    if (e == hipSuccess) {   // the trees' area sums (MptRefitInfo::area_ratio is taken against them)
+        hb.resize(6 * (size_t)T.n_nodes);
+        e = hipMemcpy(hb.data(), T.nbox, hb.size() * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && TL.nodes) {
+            hbl.resize(6 * (size_t)TL.n_nodes);
+            e = hipMemcpy(hbl.data(), TL.nbox, hbl.size() * sizeof(float), hipMemcpyDeviceToHost);
+        }
+    }
+    if (e != hipSuccess) {
+        free_lbvh(T);
+        free_lbvh(TL);
+        c->h_light_prims.clear();
+        (void)hipGetLastError();
+        return fail(MPT_ERR_HIP, std::string("mpt_upload_scene_mode: ") + hipGetErrorString(e));
+    }
+    MptRebuildInfo r{};
+    r.rebuilt = 1; r.nodes = T.n_nodes; r.records = T.n_tris; r.levels = T.depth;
+    swap_in(c->nodes, c->tris, c->nbox, c->bvh, T);
+    c->area0 = node_box_area_sum(hb.data(), c->nodes.n);
+    if (TL.nodes) {
+        r.light_rebuilt = 1; r.light_nodes = TL.n_nodes; r.light_records = TL.n_tris; r.light_levels = TL.depth;
+        swap_in(c->nodes_light, c->tris_light, c->nbox_light, c->bvh_light, TL);
+        c->area0_light = node_box_area_sum(hbl.data(), c->nodes_light.n);
+    }
+    c->mirrors_stale = true;    // the host copies of both trees follow on demand (refresh_mirrors)
+    c->topology_stale = true;
+    c->has_scene = true;
+    lap(PH_DOWNLOAD);
+    if (std::getenv("MPT_UPLOAD_STATS"))
+        std::fprintf(stderr, "mpt upload: check %.3f mirrors %.3f arrays %.3f materials %.3f build %.3f select %.3f build_light %.3f "
+                     "download %.3f ms\n", ms[PH_CHECK], ms[PH_MIRRORS], ms[PH_ARRAYS], ms[PH_MATERIALS], ms[PH_BUILD], ms[PH_SELECT],
+                     ms[PH_BUILD_LIGHT], ms[PH_DOWNLOAD]);
+    if (info) *info = r;
     return MPT_OK;
 }
 

@@ -421,8 +421,9 @@ int copy_bvh_out(const Node8* nodes, size_t n_nodes, const TriRec* tris, size_t 
                  int64_t nodes_cap, void* out_tris, int64_t tris_cap, int32_t* out_counts);
 // lbvh.hip (lbvh.h): a BVH8 over the list d_prims (device, NULL: all n primitives in order) of n
 // of the scene's n_scene_prims primitives, built on the device from idx / pos into new buffers:
-// nodes, records (flag lanes carried over from old_tris per primitive) and exact node boxes, the
-// refit's bytes included (tbox: scratch of 6 n floats).  On an error nothing is left allocated.
+// nodes, records (flag lanes carried over from old_tris per primitive, or taken from ready_flags:
+// two words per scene primitive on the device, see upload.h) and exact node boxes, the refit's
+// bytes included (tbox: scratch of 6 n floats).  On an error nothing is left allocated.
 struct LbvhDevice {
     Node8* nodes = nullptr;
     TriRec* tris = nullptr;
@@ -437,7 +438,7 @@ struct PlocStats {
 };
 hipError_t build_lbvh_device(const int32_t* d_prims, int n, int n_scene_prims, const int32_t* idx, const float* pos, float pad,
                              const TriRec* old_tris, int n_old, float* tbox, LbvhDevice& out, hipStream_t st, int mode = 0,
-                             PlocStats* stats = nullptr);
+                             PlocStats* stats = nullptr, const uint32_t* ready_flags = nullptr);
 void free_lbvh(LbvhDevice& o);
 // lbvh.hip: a[0 .. n) -> its exclusive scan; the sum of all is left in partial[ceil(n / 256)]
 hipError_t scan_u64(uint64_t* a, int n, uint64_t* partial, hipStream_t st);

@@ -131,6 +131,12 @@ void GPURenderer::set_scene(const MptScene& scene) {
     m_current_materials = m_original_materials;
 }
 
+void GPURenderer::set_scene(const MptScene& scene, int32_t build_mode, MptRebuildInfo* info) {
+    for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_upload_scene_mode(m_ctxs[k], &scene, build_mode, k == 0 ? info : nullptr));
+    m_original_materials.assign(scene.materials, scene.materials + scene.num_materials);
+    m_current_materials = m_original_materials;
+}
+
 void GPURenderer::update_materials(std::vector<MptMaterial>& materials) {
     for (MptContext* c : m_ctxs) check(mpt_update_materials(c, materials.data(), (int32_t)materials.size()));
     m_current_materials = materials;

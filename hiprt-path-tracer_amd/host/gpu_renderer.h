@@ -105,6 +105,11 @@ public:
 
     // set_scene (GPURenderer.cpp:1041-1134): the arrays are copied, the BVH8 built on upload
     void set_scene(const MptScene& scene);
+    // the same with both BVH8s built on each context's GPU (mpt_upload_scene_mode; build_mode:
+    // MPT_BUILD_LBVH, MPT_BUILD_PLOC or MPT_BUILD_SAH): a topology change at interactive rates.
+    // info (optional): the first context's report.  Reset the accumulation afterwards, as after
+    // any set_scene.
+    void set_scene(const MptScene& scene, int32_t build_mode, MptRebuildInfo* info = nullptr);
     // set_envmap (GPURenderer.cpp:1136-1174): RGBA32F equirect; alias table and CDF built here
     void set_envmap(const float* rgba, int width, int height, const std::string& envmap_filepath = "");
     bool has_envmap() const { return m_has_envmap; }

@@ -36,7 +36,7 @@ SYMBOLS = [
     "mpt_display_settings_default", "mpt_display_uniforms", "mpt_display", "mpt_display_host", "mpt_write_png",
     "mpt_denoise_settings_default", "mpt_denoise", "mpt_denoised_buffer", "mpt_denoise_device", "mpt_denoise_host",
     "mpt_update_vertices", "mpt_get_bvh", "mpt_bvh_refit_host", "mpt_rebuild_bvh", "mpt_bvh_build_host",
-    "mpt_rebuild_bvh_mode", "mpt_bvh_build_host_mode",
+    "mpt_rebuild_bvh_mode", "mpt_bvh_build_host_mode", "mpt_upload_scene_mode",
 ]
 
 
@@ -123,6 +123,7 @@ def lib() -> C.CDLL:
     L.mpt_bvh_build_host.argtypes = [vp, i32, vp, i32, vp, i32, vp, C.c_int64, vp, C.c_int64, vp]
     L.mpt_rebuild_bvh_mode.argtypes = [vp, i32, C.POINTER(abi.RebuildInfo)]
     L.mpt_bvh_build_host_mode.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64, vp, C.c_int64, vp]
+    L.mpt_upload_scene_mode.argtypes = [vp, C.POINTER(abi.Scene), i32, C.POINTER(abi.RebuildInfo)]
     _lib = L
     return L
 
@@ -335,11 +336,23 @@ class GPURenderer:
         self._n_mats = 0
 
     # --- scene / resources -----------------------------------------------------
-    def set_scene(self, sd: "scene.SceneData"):
-        """GPURenderer::set_scene (GPURenderer.cpp:1052-1130)."""
+    def set_scene(self, sd: "scene.SceneData", build=None, info=False):
+        """GPURenderer::set_scene (GPURenderer.cpp:1052-1130).  build=None: mpt_upload_scene, both
+        BVHs by the host builder.  build=abi.BUILD_LBVH / BUILD_PLOC / BUILD_SAH:
+        mpt_upload_scene_mode, both BVHs built on the GPU in that mode (the way to change topology
+        at interactive rates); info=True then returns the abi.RebuildInfo, else None."""
+        if build is not None and (isinstance(build, bool) or not isinstance(build, (int, np.integer))):
+            # (an integer that is no mode, such as 2, is the library's to refuse: MPT_ERR_INVALID_ARGUMENT)
+            raise TypeError(f"set_scene: build must be None or an abi.BUILD_* mode, not {build!r}")
         s = sd.to_abi()
-        _check(lib().mpt_upload_scene(self.h, C.byref(s)))
+        ri = None
+        if build is None:
+            _check(lib().mpt_upload_scene(self.h, C.byref(s)))
+        else:
+            ri = abi.RebuildInfo() if info else None
+            _check(lib().mpt_upload_scene_mode(self.h, C.byref(s), int(build), C.byref(ri) if info else None))
         self._n_mats = len(sd.materials)
+        return ri
 
     def update_materials(self, materials):
         arr = (abi.Material * len(materials))(*materials)

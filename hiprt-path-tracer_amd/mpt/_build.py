@@ -19,7 +19,7 @@ INCLUDE = ROOT.parent / "include"
 LIB_PATH = PKG_DIR / "libmpt.so"
 OBJ_DIR = CSRC / "build"
 
-SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp", "display.hip", "denoise.hip", "refit.hip", "lbvh.hip", "ploc.hip", "sah.hip"]
+SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp", "display.hip", "denoise.hip", "refit.hip", "lbvh.hip", "ploc.hip", "sah.hip", "upload.hip"]
 # mpt_part.hip is compiled once per part (-DMPT_TU_PART=k): the shading and ReSTIR DI kernel
 # instantiations, so that they compile in parallel with the rest
 PARTS = [1, 2, 3, 4, 5, 6, 7]
@@ -93,6 +93,9 @@ REBUILD_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" 
 # GPURenderer::rebuild_bvh in PLOC mode (tests/test_ploc_host_cpp.py)
 PLOC_TEST = HOST_DIR / "ploc_move"
 PLOC_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "ploc_move.cpp"]
+# GPURenderer::set_scene with a build mode (tests/test_upload_host_cpp.py)
+UPLOAD_TEST = HOST_DIR / "upload_mode"
+UPLOAD_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "upload_mode.cpp"]
 
 
 def _build_driver(exe: Path, sources, lib: Path, verbose: bool) -> Path:
@@ -115,7 +118,8 @@ def _build_driver(exe: Path, sources, lib: Path, verbose: bool) -> Path:
 def build_host_test(verbose: bool = True) -> Path:
     """The C++ GPURenderer mirror (host/) linked with libmpt into the test drivers of
     tests/test_host_cpp.py, tests/test_display_host_cpp.py, tests/test_denoise_host_cpp.py and
-    tests/test_refit_host_cpp.py, tests/test_rebuild_host_cpp.py, tests/test_ploc_host_cpp.py
+    tests/test_refit_host_cpp.py, tests/test_rebuild_host_cpp.py, tests/test_ploc_host_cpp.py,
+    tests/test_upload_host_cpp.py
     (plain g++: the host side is ordinary C++ over the C ABI)."""
     lib = build(verbose=verbose)
     _build_driver(DENOISE_TEST, DENOISE_SOURCES, lib, verbose)
@@ -123,6 +127,7 @@ def build_host_test(verbose: bool = True) -> Path:
     _build_driver(REFIT_TEST, REFIT_SOURCES, lib, verbose)
     _build_driver(REBUILD_TEST, REBUILD_SOURCES, lib, verbose)
     _build_driver(PLOC_TEST, PLOC_SOURCES, lib, verbose)
+    _build_driver(UPLOAD_TEST, UPLOAD_SOURCES, lib, verbose)
     return _build_driver(HOST_TEST, HOST_SOURCES, lib, verbose)
 
 

@@ -10,6 +10,8 @@
  *   mpt_upload_scene              <- GPURenderer::set_scene -> set_hiprt_scene_from_scene
  *                                    (GPURenderer.h:220, GPURenderer.cpp:1041-1134) and
  *                                    HIPRTGeometry::build_bvh (HIPRTScene.h:60-87)
+ *   mpt_upload_scene_mode         <- the same, with both BVH8s built on the GPU in a build mode
+ *                                    (HIPRT builds its geometry on the device as well)
  *   mpt_update_materials          <- GPURenderer::update_materials (GPURenderer.h:228)
  *   mpt_update_vertices           <- (no counterpart: the reference rebuilds its HIPRT geometry) moved
  *                                    vertices with a GPU refit of both BVH8s
@@ -648,6 +650,27 @@ int mpt_rebuild_bvh(MptContext* ctx, MptRebuildInfo* info_or_NULL);
  * global memory) instead of one wave per node: the same bytes.  MPT_SAH_DEPTH=d (both entry points)
  * lowers the depth below which mode 3 splits by count only, 40: a test hook. */
 int mpt_rebuild_bvh_mode(MptContext* ctx, int32_t mode, MptRebuildInfo* info_or_NULL);
+/* mpt_upload_scene with both BVH8s built on the GPU in a build mode (DESIGN.md §2 "Uploads with a
+ * build mode"): the way to change topology -- an object added or removed, another index list,
+ * another emissive list, a new scene -- without the host builder.  The call takes over the context
+ * as mpt_upload_scene does: the same argument checks and messages, the same device arrays, box pad,
+ * per-triangle attributes, resolved materials and emissive table.  No tree is built on the host:
+ * the scene tree is built over all primitives as mpt_rebuild_bvh_mode builds it; the light-hit
+ * tree's primitives (those whose material can emit, ascending) are selected on the device and the
+ * tree built over them in the same mode; the records' flag lanes (alpha test, material class) are
+ * written by the build from per-primitive words made on the device.  The trees' bytes are those of
+ * mpt_bvh_build_host_mode, the flag lanes those after mpt_upload_scene.
+ * The scene tree must fit the traversal stack bound as in mpt_rebuild_bvh (2 * levels + 2; no
+ * shallower fallback): else MPT_ERR_UNSUPPORTED.  A light-hit tree that does not fit is dropped as
+ * mpt_upload_scene drops it; one that cannot be allocated is an optimisation lost, not an error.
+ * A NULL argument, a scene that mpt_upload_scene refuses or an unknown mode (2 among them) returns
+ * MPT_ERR_INVALID_ARGUMENT and changes nothing.  MPT_ERR_UNSUPPORTED or MPT_ERR_HIP leaves the context WITHOUT a scene (its arrays are already the new
+ * scene's): upload again.  info is filled as by mpt_rebuild_bvh_mode.  Afterwards
+ * mpt_update_materials, mpt_update_vertices (area ratios against these trees), mpt_rebuild_bvh_mode
+ * and mpt_get_bvh work as after a rebuild.  As after any upload, the next frame must carry
+ * need_to_reset.  MPT_UPLOAD_STATS in the environment (read at the call) prints the wall time of
+ * the call's phases to stderr: a measuring aid. */
+int mpt_upload_scene_mode(MptContext* ctx, const MptScene* scene, int32_t mode, MptRebuildInfo* info_or_NULL);
 /* No device needed: the host loop of the same definition over the list prims (NULL: all
  * num_triangles primitives in order; else num_prims > 0 scene primitive indices) -- the bytes
  * mpt_get_bvh returns after mpt_rebuild_bvh, except the records' two flag lanes, which are 0 here
