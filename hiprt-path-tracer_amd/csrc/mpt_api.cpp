@@ -182,6 +182,15 @@ struct MptContext {
     // records and node boxes follow with the next refresh_mirrors (level_begin and depth at once)
     bool topology_stale = false;
     std::vector<uint8_t> h_vert_used;
+    // per-object motion (mpt_set_objects, xform.hip): the object id of every vertex (-1: static),
+    // the rest pose captured when the objects were set, the staging arrays a transform writes
+    // before they are swapped in for pos / nrm, the objects' 21-float records, h_vert_used on the
+    // device (mpt_update_vertices_device reads it as well) and the two reduction words
+    int num_objects = -1;                 // -1: no objects set
+    DBuf<int32_t> vert_obj;
+    DBuf<float> rest_pos, rest_nrm, stage_pos, stage_nrm, xf_recs;
+    DBuf<uint8_t> vert_used;
+    DBuf<uint32_t> xf_red;
     int refit_host_loop = 0;              // test hook (MPT_REFIT_HOST): the refit by the host loop of refit.h
     int light_bvh = 1;                    // MPT_LIGHT_BVH at mpt_create: 0 = one closest-hit traversal per light-hit query
     bool light_bvh_ok = false;            // the light BVH matches the materials (else: the exact closest-hit path)
@@ -1186,6 +1195,12 @@ static int check_scene(const MptScene* s) {
     return MPT_OK;
 }
 
+// The object table of mpt_set_objects, its rest pose and the staging arrays freed.
+static void drop_objects(MptContext* c) {
+    c->num_objects = -1;
+    release_all(c->vert_obj, c->rest_pos, c->rest_nrm, c->stage_pos, c->stage_nrm, c->xf_recs);
+}
+
 // What a scene upload keeps on the host besides its trees: the box pad, the vertices in use, the
 // copies of indices and positions; no light set yet.
 static void take_scene_mirrors(MptContext* c, const MptScene* s) {
@@ -1197,6 +1212,8 @@ static void take_scene_mirrors(MptContext* c, const MptScene* s) {
     c->h_light_prims.clear();
     c->nodes_light.release();
     c->tris_light.release();
+    drop_objects(c);          // a new scene: the objects and the rest pose were the old one's
+    c->vert_used.release();
 }
 
 static int upload_scene_arrays(MptContext* c, const MptScene* s);
@@ -1305,18 +1322,28 @@ int mpt_update_materials(MptContext* c, const MptMaterial* m, int32_t count) {
 
 namespace {
 
-// The device side of mpt_update_vertices: uploads, the refit of both trees, the tables derived
-// from the positions.  Any HIP error is returned; the caller then drops the scene.
-hipError_t update_vertices_device(MptContext* c, const float* v, const float* nrm, float pad) {
+// The upload step of mpt_update_vertices: the streams drained, the host arrays copied over the
+// context's.  Any HIP error is returned; the caller then drops the scene.
+hipError_t upload_vertices(MptContext* c, const float* v, const float* nrm) {
+    hipStream_t st = c->stream;
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->pos.p, v, c->pos.n * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nrm) e = hipMemcpyAsync(c->nrm.p, nrm, c->nrm.n * sizeof(float), hipMemcpyHostToDevice, st);
+    return e;
+}
+
+// The tail of every geometry update, once pos / nrm hold the new arrays on the device: the refit
+// of both trees and the tables derived from the positions.  host_v: the same positions on the host
+// for the MPT_REFIT_HOST test hook (NULL: always the kernels -- mpt_update_transforms and
+// mpt_update_vertices_device have no host array).
+hipError_t refit_and_tables(MptContext* c, float pad, const float* host_v) {
 #define UV(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
     hipStream_t st = c->stream;
-    UV(drain(c));
+    const float* v = host_v;
     const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
-    UV(hipMemcpyAsync(c->pos.p, v, c->pos.n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (nrm) UV(hipMemcpyAsync(c->nrm.p, nrm, c->nrm.n * sizeof(float), hipMemcpyHostToDevice, st));
     UV(c->nbox.alloc(6 * c->nodes.n));
     if (light) UV(c->nbox_light.alloc(6 * c->nodes_light.n));
-    if (c->refit_host_loop) {
+    if (c->refit_host_loop && v) {
         // (the host copies' w lanes are always current; their positions are rewritten here; after
         // a rebuild on the device the copies first take the new trees)
         if (c->topology_stale && refresh_mirrors(c) != MPT_OK) return hipErrorUnknown;
@@ -1353,6 +1380,65 @@ hipError_t update_vertices_device(MptContext* c, const float* v, const float* nr
 #undef UV
 }
 
+// The end of every geometry update: e is what the device side returned.  On success the report
+// (a download of the exact node boxes, only when asked for); on a HIP error the scene is dropped.
+int finish_update(MptContext* c, hipError_t e, MptRefitInfo* info, const char* who) {
+    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
+    std::vector<float> hb, hbl;
+    if (e == hipSuccess && info) {
+        hb.resize(c->nbox.n);
+        e = hipMemcpy(hb.data(), c->nbox.p, hb.size() * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && light) {
+            hbl.resize(c->nbox_light.n);
+            e = hipMemcpy(hbl.data(), c->nbox_light.p, hbl.size() * sizeof(float), hipMemcpyDeviceToHost);
+        }
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->has_scene = false;   // half updated: the caller uploads again
+        return fail(MPT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    if (info) {
+        MptRefitInfo r{};
+        r.nodes = (int32_t)c->nodes.n;
+        r.levels = c->bvh.depth;
+        r.area_ratio = (float)(node_box_area_sum(hb.data(), c->nodes.n) / c->area0);
+        if (light) {
+            r.light_nodes = (int32_t)c->nodes_light.n;
+            r.light_levels = c->bvh_light.depth;
+            r.light_area_ratio = (float)(node_box_area_sum(hbl.data(), c->nodes_light.n) / c->area0_light);
+        }
+        *info = r;
+    }
+    return MPT_OK;
+}
+
+// h_vert_used on the device (the pad's maximum is taken over the vertices in use).
+hipError_t ensure_used_mask(MptContext* c) {
+    if (c->vert_used.p && c->vert_used.n == c->h_vert_used.size()) return hipSuccess;
+    hipError_t e = c->vert_used.upload(c->h_vert_used.data(), c->h_vert_used.size(), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) c->vert_used.release();
+    return e;
+}
+
+// The two words a reduction of xform.hip left: the maximum's bits and the non-finite flag.
+hipError_t read_reduction(MptContext* c, float* max_abs, bool* bad) {
+    uint32_t w[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(w, c->xf_red.p, sizeof(w), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    std::memcpy(max_abs, &w[0], 4);
+    *bad = w[1] != 0;
+    return e;
+}
+
+// vertices per lane of the xform kernels: 4 (MPT_XFORM_GROUP=1 in the environment, read at the
+// call: dword accesses, the same bytes -- tools/xform_time.py measures both)
+int xform_group() {
+    const char* e = std::getenv("MPT_XFORM_GROUP");
+    return e && std::atoi(e) == 1 ? 1 : 4;
+}
+
 }  // namespace
 
 int mpt_update_vertices(MptContext* c, const float* vertices, const float* vertex_normals, int32_t num_vertices,
@@ -1374,35 +1460,125 @@ int mpt_update_vertices(MptContext* c, const float* vertices, const float* verte
     const float pad = std::ldexp(std::max(m, 1.0f), -20);
     HIPCHK(hipSetDevice(c->device));
     c->box_pad = pad;
-    hipError_t e = update_vertices_device(c, vertices, vertex_normals, pad);
-    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
-    std::vector<float> hb, hbl;
-    if (e == hipSuccess && info) {
-        hb.resize(c->nbox.n);
-        e = hipMemcpy(hb.data(), c->nbox.p, hb.size() * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && light) {
-            hbl.resize(c->nbox_light.n);
-            e = hipMemcpy(hbl.data(), c->nbox_light.p, hbl.size() * sizeof(float), hipMemcpyDeviceToHost);
-        }
+    hipError_t e = upload_vertices(c, vertices, vertex_normals);
+    if (e == hipSuccess) e = refit_and_tables(c, pad, vertices);
+    return finish_update(c, e, info, "mpt_update_vertices");
+}
+
+int mpt_set_objects(MptContext* c, const int32_t* vertex_object, int32_t num_vertices, int32_t num_objects) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!vertex_object) {
+        if (num_objects != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+        HIPCHK(hipSetDevice(c->device));
+        drop_objects(c);
+        return MPT_OK;
     }
+    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
+    if (num_objects <= 0) return fail(MPT_ERR_INVALID_ARGUMENT, "objects: bad object count");
+    for (int32_t i = 0; i < num_vertices; i++)
+        if (vertex_object[i] < -1 || vertex_object[i] >= num_objects) return fail(MPT_ERR_INVALID_ARGUMENT, "object id out of range");
+    HIPCHK(hipSetDevice(c->device));
+    // into new buffers, swapped in when all of them are there: a failure leaves the old objects
+    DBuf<int32_t> ids;
+    DBuf<float> rp, rn;
+    hipStream_t st = c->stream;
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = ensure_used_mask(c);
+    if (e == hipSuccess) e = ids.upload(vertex_object, (size_t)num_vertices, st);
+    if (e == hipSuccess) e = rp.alloc(c->pos.n);
+    if (e == hipSuccess) e = rn.alloc(c->nrm.n);
+    if (e == hipSuccess) e = hipMemcpyAsync(rp.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rn.p, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        c->has_scene = false;   // half updated: the caller uploads again
-        return fail(MPT_ERR_HIP, std::string("mpt_update_vertices: ") + hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_objects: ") + hipGetErrorString(e));
     }
-    if (info) {
-        MptRefitInfo r{};
-        r.nodes = (int32_t)c->nodes.n;
-        r.levels = c->bvh.depth;
-        r.area_ratio = (float)(node_box_area_sum(hb.data(), c->nodes.n) / c->area0);
-        if (light) {
-            r.light_nodes = (int32_t)c->nodes_light.n;
-            r.light_levels = c->bvh_light.depth;
-            r.light_area_ratio = (float)(node_box_area_sum(hbl.data(), c->nodes_light.n) / c->area0_light);
-        }
-        *info = r;
-    }
+    drop_objects(c);
+    std::swap(c->vert_obj.p, ids.p); std::swap(c->vert_obj.n, ids.n);
+    std::swap(c->rest_pos.p, rp.p); std::swap(c->rest_pos.n, rp.n);
+    std::swap(c->rest_nrm.p, rn.p); std::swap(c->rest_nrm.n, rn.n);
+    c->num_objects = num_objects;
     return MPT_OK;
+}
+
+int mpt_update_transforms(MptContext* c, const float* matrices, int32_t num_objects, MptRefitInfo* info) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!matrices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (c->num_objects < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no objects set");
+    if (num_objects != c->num_objects) return fail(MPT_ERR_INVALID_ARGUMENT, "object count differs from the table's");
+    if (!matrices_finite(matrices, num_objects)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite matrix entry");
+    if (c->rest_pos.n != c->pos.n || c->rest_nrm.n != c->nrm.n || 3 * c->vert_obj.n != c->pos.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "objects do not fit the scene");
+    std::vector<float> recs;
+    make_xform_records(matrices, num_objects, recs);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    float m = 0.0f;
+    bool bad = false;
+    // everything up to the swap writes scratch only: a refusal or an error here changes nothing
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = ensure_used_mask(c);
+    if (e == hipSuccess) e = c->stage_pos.alloc(c->pos.n);
+    if (e == hipSuccess) e = c->stage_nrm.alloc(c->nrm.n);
+    if (e == hipSuccess) e = c->xf_red.alloc(2);
+    if (e == hipSuccess) e = c->xf_recs.upload(recs.data(), recs.size(), st);
+    if (e == hipSuccess)
+        e = launch_xform(c->rest_pos.p, c->rest_nrm.p, c->vert_obj.p, c->vert_used.p, c->xf_recs.p, (int)c->vert_obj.n,
+                         c->stage_pos.p, c->stage_nrm.p, c->xf_red.p, xform_group(), st);
+    if (e == hipSuccess) e = read_reduction(c, &m, &bad);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->has_scene = false;
+        return fail(MPT_ERR_HIP, std::string("mpt_update_transforms: ") + hipGetErrorString(e));
+    }
+    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
+    std::swap(c->pos.p, c->stage_pos.p);
+    std::swap(c->nrm.p, c->stage_nrm.p);
+    const float pad = std::ldexp(std::max(m, 1.0f), -20);
+    c->box_pad = pad;
+    return finish_update(c, refit_and_tables(c, pad, nullptr), info, "mpt_update_transforms");
+}
+
+int mpt_update_vertices_device(MptContext* c, const float* d_vertices, const float* d_normals, int32_t num_vertices,
+                               MptRefitInfo* info) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!d_vertices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
+    HIPCHK(hipSetDevice(c->device));
+    for (const float* p : {d_vertices, d_normals}) {   // a host pointer must not reach a kernel
+        if (!p) continue;
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
+            (void)hipGetLastError();
+            return fail(MPT_ERR_INVALID_ARGUMENT, "not memory of the context's device");
+        }
+    }
+    hipStream_t st = c->stream;
+    float m = 0.0f;
+    bool bad = false;
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = ensure_used_mask(c);
+    if (e == hipSuccess) e = c->xf_red.alloc(2);
+    if (e == hipSuccess) e = launch_xform_check(d_vertices, c->vert_used.p, num_vertices, c->xf_red.p, xform_group(), st);
+    if (e == hipSuccess) e = read_reduction(c, &m, &bad);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->has_scene = false;
+        return fail(MPT_ERR_HIP, std::string("mpt_update_vertices_device: ") + hipGetErrorString(e));
+    }
+    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
+    const float pad = std::ldexp(std::max(m, 1.0f), -20);
+    c->box_pad = pad;
+    e = hipMemcpyAsync(c->pos.p, d_vertices, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && d_normals) e = hipMemcpyAsync(c->nrm.p, d_normals, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = refit_and_tables(c, pad, nullptr);
+    return finish_update(c, e, info, "mpt_update_vertices_device");
 }
 
 // A tree built on the device takes the place of the context's: the buffers change hands, the host

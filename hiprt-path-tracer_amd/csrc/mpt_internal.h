@@ -414,6 +414,21 @@ hipError_t launch_denoise(const MptDenoiseSettings& S, const float* color, const
 hipError_t launch_refit_tris(TriRec* tris, int n, const int32_t* idx, const float* pos, float pad, float* tbox, hipStream_t st);
 hipError_t launch_refit_levels(Node8* nodes, float* node_box, const float* tbox, const int32_t* level_begin, int levels,
                                hipStream_t st);
+// xform.hip (xform.h): n rest-pose vertices moved by their objects' 21-float records (obj: -1 or a
+// record index per vertex) into out_pos / out_nrm; red: two device words, zeroed on the stream
+// first, then the bits of the largest |coordinate| over the vertices with a non-zero used byte and
+// 1 when any output coordinate is not finite.  group: vertices per lane, 4 (16-byte accesses;
+// falls back to 1 for arrays that are not 16-byte aligned) or 1.  launch_xform_check: the same
+// reduction over positions that are already there.
+hipError_t launch_xform(const float* rest_pos, const float* rest_nrm, const int32_t* obj, const uint8_t* used, const float* recs,
+                        int n, float* out_pos, float* out_nrm, uint32_t* red, int group, hipStream_t st);
+hipError_t launch_xform_check(const float* pos, const uint8_t* used, int n, uint32_t* red, int group, hipStream_t st);
+// the host loop of the same arithmetic (false: a non-finite output coordinate); the checks and the
+// records (12 floats per object -> 21) both paths share
+bool transform_host(const float* rest_pos, const float* rest_nrm, const int32_t* obj, size_t n, const float* recs, float* out_pos,
+                    float* out_nrm);
+bool matrices_finite(const float* matrices, int32_t num_objects);
+void make_xform_records(const float* matrices, int32_t num_objects, std::vector<float>& recs);
 // the scene BVH as mpt_upload_scene builds it (rebuilt shallower while too deep for stack_limit
 // entries); returns the stack limit in force (MPT_BVH_MAX_STACK)
 int build_scene_bvh8(const float* vertices, const int32_t* indices, int32_t num_triangles, BVH8& out, int stack_limit);

@@ -149,6 +149,15 @@ void GPURenderer::update_vertices(const float* vertices, const float* vertex_nor
     reset();   // samples, reservoirs and adaptive counters of the old geometry are stale
 }
 
+void GPURenderer::set_objects(const int32_t* vertex_object, int32_t num_vertices, int32_t num_objects) {
+    for (MptContext* c : m_ctxs) check(mpt_set_objects(c, vertex_object, num_vertices, num_objects));
+}
+
+void GPURenderer::update_transforms(const float* matrices, int32_t num_objects, MptRefitInfo* info) {
+    for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_update_transforms(m_ctxs[k], matrices, num_objects, k == 0 ? info : nullptr));
+    reset();   // as update_vertices: what was accumulated shows the old geometry
+}
+
 void GPURenderer::rebuild_bvh(MptRebuildInfo* info, int32_t mode) {
     for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_rebuild_bvh_mode(m_ctxs[k], mode, k == 0 ? info : nullptr));
     // (no reset: results do not depend on the tree)

@@ -132,6 +132,14 @@ public:
     // render carries need_to_reset, as after reset().  info (optional): the first context's report.
     void update_vertices(const float* vertices, const float* vertex_normals_or_null, int32_t num_vertices,
                          MptRefitInfo* info = nullptr);
+    // set_objects / update_transforms (no counterpart in the reference): per-object motion of the
+    // flat scene.  set_objects gives every context the object of each vertex (-1: static; NULL
+    // with 0 objects removes the table) and captures the rest pose on its GPU (mpt_set_objects);
+    // update_transforms moves the rest pose by one row-major 3x4 matrix per object on every
+    // context's GPU and refits its BVHs (mpt_update_transforms).  The accumulation restarts as after
+    // update_vertices.  info (optional): the first context's report.
+    void set_objects(const int32_t* vertex_object, int32_t num_vertices, int32_t num_objects);
+    void update_transforms(const float* matrices, int32_t num_objects, MptRefitInfo* info = nullptr);
     // rebuild_bvh (no counterpart in the reference): every context rebuilds its BVHs on its GPU
     // from the positions it holds (mpt_rebuild_bvh_mode), e.g. once update_vertices reports a large
     // area_ratio.  The accumulation continues: traversal results do not depend on the tree.

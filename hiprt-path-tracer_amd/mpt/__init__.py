@@ -22,7 +22,7 @@ from . import scene
 from ._build import LIB_PATH
 
 __all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
-           "display_host", "write_png", "denoise_host", "bvh_refit_host", "bvh_build_host"]
+           "display_host", "write_png", "denoise_host", "bvh_refit_host", "bvh_build_host", "transform_host"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -37,6 +37,7 @@ SYMBOLS = [
     "mpt_denoise_settings_default", "mpt_denoise", "mpt_denoised_buffer", "mpt_denoise_device", "mpt_denoise_host",
     "mpt_update_vertices", "mpt_get_bvh", "mpt_bvh_refit_host", "mpt_rebuild_bvh", "mpt_bvh_build_host",
     "mpt_rebuild_bvh_mode", "mpt_bvh_build_host_mode", "mpt_upload_scene_mode",
+    "mpt_set_objects", "mpt_update_transforms", "mpt_update_vertices_device", "mpt_transform_host",
 ]
 
 
@@ -124,6 +125,10 @@ def lib() -> C.CDLL:
     L.mpt_rebuild_bvh_mode.argtypes = [vp, i32, C.POINTER(abi.RebuildInfo)]
     L.mpt_bvh_build_host_mode.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64, vp, C.c_int64, vp]
     L.mpt_upload_scene_mode.argtypes = [vp, C.POINTER(abi.Scene), i32, C.POINTER(abi.RebuildInfo)]
+    L.mpt_set_objects.argtypes = [vp, vp, i32, i32]
+    L.mpt_update_transforms.argtypes = [vp, vp, i32, C.POINTER(abi.RefitInfo)]
+    L.mpt_update_vertices_device.argtypes = [vp, vp, vp, i32, C.POINTER(abi.RefitInfo)]
+    L.mpt_transform_host.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
     _lib = L
     return L
 
@@ -323,6 +328,38 @@ def bvh_build_host(vertices, indices, prims=None, mode=abi.BUILD_LBVH):
                                                                            n, nc, t, tc, cnt))
 
 
+def _matrices(matrices, who):
+    """[K, 3, 4] or [K, 4, 4] (the bottom row dropped) -> contiguous float32 [K, 3, 4]."""
+    m = np.asarray(matrices, np.float32)
+    if m.ndim != 3 or m.shape[1:] not in ((3, 4), (4, 4)):
+        raise ValueError(f"{who}: matrices of shape {m.shape}, not [K, 3, 4] or [K, 4, 4]")
+    return np.ascontiguousarray(m[:, :3, :])
+
+
+def transform_host(rest_vertices, rest_normals, vertex_object, matrices):
+    """mpt_transform_host, no GPU: the host loop of csrc/xform.h -- the positions ([V, 3] float32)
+    and, when rest_normals is given, the vertex normals that GPURenderer.update_transforms(matrices)
+    leaves on the device for this rest pose and object table (vertex_object: int32 [V], -1 for
+    static vertices; matrices: [K, 3, 4] or [K, 4, 4]).  Returns (vertices, normals or None)."""
+    v = np.ascontiguousarray(rest_vertices, np.float32).reshape(-1, 3)
+    n = None if rest_normals is None else np.ascontiguousarray(rest_normals, np.float32).reshape(-1, 3)
+    if n is not None and n.shape != v.shape:
+        raise ValueError(f"transform_host: {n.shape[0]} normals for {v.shape[0]} vertices")
+    ids = np.ascontiguousarray(vertex_object, np.int32).reshape(-1)
+    if len(ids) != len(v):
+        raise ValueError(f"transform_host: {len(ids)} object ids for {len(v)} vertices")
+    m = _matrices(matrices, "transform_host")
+    ov = np.empty_like(v)
+    on = None if n is None else np.empty_like(n)
+    _check(lib().mpt_transform_host(_p(v), _p(n), _p(ids), len(v), _p(m), len(m), _p(ov), _p(on)))
+    return ov, on
+
+
+def _on_device(a):
+    """A torch tensor in GPU memory (anything else, a CPU tensor included, is a host array)."""
+    return bool(getattr(a, "is_cuda", False))
+
+
 class GPURenderer:
     """One renderer context on one GPU (GPURenderer.h:69)."""
 
@@ -362,7 +399,12 @@ class GPURenderer:
         """mpt_update_vertices: new positions ([V, 3] float32, the scene's vertex count) and
         optionally new vertex normals for the uploaded scene; both BVHs are refitted on the GPU.
         The next frame must carry need_to_reset (sample_number 0).  info=True returns the
-        abi.RefitInfo (a download of the node boxes), else None."""
+        abi.RefitInfo (a download of the node boxes), else None.
+        Torch tensors on the context's device (positions, or positions and normals) go through
+        mpt_update_vertices_device: no copy to the host and back.  A mix of host and device arrays
+        raises TypeError."""
+        if _on_device(vertices) or _on_device(normals):
+            return self._update_vertices_device(vertices, normals, info)
         v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
         n = None
         if normals is not None:
@@ -371,6 +413,50 @@ class GPURenderer:
                 raise ValueError(f"update_vertices: {n.shape[0]} normals for {v.shape[0]} vertices")
         ri = abi.RefitInfo() if info else None
         _check(lib().mpt_update_vertices(self.h, _p(v), _p(n), v.shape[0], C.byref(ri) if info else None))
+        return ri
+
+    def _update_vertices_device(self, vertices, normals, info):
+        import torch
+        if not _on_device(vertices) or (normals is not None and not _on_device(normals)):
+            raise TypeError("update_vertices: positions and normals must both be host arrays or both device tensors")
+        ts = []
+        for t in (vertices, normals):
+            if t is None:
+                ts.append(None)
+                continue
+            if t.device.index != self.device:
+                raise ValueError(f"update_vertices: tensor on {t.device}, the context is on device {self.device}")
+            ts.append(t.to(torch.float32).contiguous().reshape(-1, 3))
+        v, n = ts
+        if n is not None and n.shape != v.shape:
+            raise ValueError(f"update_vertices: {n.shape[0]} normals for {v.shape[0]} vertices")
+        # the library reads on its own stream: what torch has enqueued for the tensors must be done
+        torch.cuda.current_stream(v.device).synchronize()
+        ri = abi.RefitInfo() if info else None
+        _check(lib().mpt_update_vertices_device(self.h, C.c_void_p(v.data_ptr()), C.c_void_p(n.data_ptr()) if n is not None else None,
+                                                v.shape[0], C.byref(ri) if info else None))
+        return ri
+
+    def set_objects(self, vertex_object, num_objects=None):
+        """mpt_set_objects: vertex_object is int32 [V], the object of every vertex of the scene in
+        [-1, num_objects) (-1: static; num_objects=None: the largest id + 1).  Captures the rest
+        pose -- the positions and normals on the device now -- which every update_transforms
+        moves.  vertex_object=None removes the objects."""
+        if vertex_object is None:
+            _check(lib().mpt_set_objects(self.h, None, 0, 0))
+            return
+        ids = np.ascontiguousarray(vertex_object, np.int32).reshape(-1)
+        k = int(ids.max()) + 1 if num_objects is None else int(num_objects)
+        _check(lib().mpt_set_objects(self.h, _p(ids), len(ids), k))
+
+    def update_transforms(self, matrices, info=False):
+        """mpt_update_transforms: one matrix per object ([K, 3, 4], or [K, 4, 4] whose bottom row is
+        dropped) applied to the rest pose on the GPU, then the refit of both BVHs: 48 bytes per
+        object cross the bus, no vertex array.  The next frame must carry need_to_reset.
+        info=True returns the abi.RefitInfo, else None."""
+        m = _matrices(matrices, "update_transforms")
+        ri = abi.RefitInfo() if info else None
+        _check(lib().mpt_update_transforms(self.h, _p(m), len(m), C.byref(ri) if info else None))
         return ri
 
     def rebuild_bvh(self, info=False, mode=abi.BUILD_LBVH):

@@ -66,6 +66,7 @@ class SceneData:
         self.emissive = None          # int32 [E]
         self.textures = []            # list of uint8 [h, w, 4]
         self.camera_info = None       # dict for make_camera
+        self.vertex_object = None     # int32 [V] or None: per vertex the ordinal of its mesh node (glTF loader)
         self.name = ""
 
     @property
@@ -387,9 +388,12 @@ def load_gltf(path, aspect_override=None):
     # instances: (material, positions, normals or None, texcoords or None, indices)
     inst = []
     need_default = False
+    n_mesh_nodes = 0
     for ni, n in enumerate(g["nodes"]):
         if "mesh" not in n or ni not in world:
             continue
+        node_ord = n_mesh_nodes          # SceneData.vertex_object: the ordinal among the mesh nodes
+        n_mesh_nodes += 1
         M = world[ni]
         R = M[:3, :3]
         RIT = np.linalg.inv(R).T
@@ -417,7 +421,7 @@ def load_gltf(path, aspect_override=None):
             if mi is None:
                 need_default = True
                 mi = n_mat
-            inst.append((mi, pos, nrm, uv, _triangles(mode, idx)))
+            inst.append((mi, pos, nrm, uv, _triangles(mode, idx), node_ord))
 
     total_mats = n_mat + (1 if need_default else 0)
     tex_idx, const_em, textures, tex_count = _load_textures(g, bins, base, materials_json)
@@ -431,11 +435,11 @@ def load_gltf(path, aspect_override=None):
 
     sd = SceneData()
     sd.name = os.path.splitext(os.path.basename(path))[0]
-    tri, verts, nrms, hasn, uvs, mids = [], [], [], [], [], []
+    tri, verts, nrms, hasn, uvs, mids, vobj = [], [], [], [], [], [], []
     voff = 0
     # PreTransformVertices: output meshes ordered by material index
     for mi in range(total_mats):
-        for (m, pos, nrm, uv, idx) in inst:
+        for (m, pos, nrm, uv, idx, node_ord) in inst:
             if m != mi:
                 continue
             tri.append(idx + voff)
@@ -449,6 +453,7 @@ def load_gltf(path, aspect_override=None):
             else:
                 uvs.append(np.zeros((len(pos), 2), np.float32))
             mids.append(np.full(len(idx), mi, np.int32))
+            vobj.append(np.full(len(pos), node_ord, np.int32))
             voff += len(pos)
     sd.triangle_indices = np.concatenate(tri).astype(np.int32).ravel()
     sd.vertices = np.concatenate(verts).astype(np.float32)
@@ -456,6 +461,7 @@ def load_gltf(path, aspect_override=None):
     sd.has_normals = np.concatenate(hasn)
     sd.texcoords = np.concatenate(uvs)
     sd.material_indices = np.concatenate(mids)
+    sd.vertex_object = np.concatenate(vobj)
     sd.materials = mats
     sd.textures = textures
 

@@ -594,6 +594,61 @@ typedef struct MptRefitInfo {
  * about it. */
 int mpt_update_vertices(MptContext* ctx, const float* vertices, const float* vertex_normals_or_NULL,
                         int32_t num_vertices, MptRefitInfo* info_or_NULL);
+/* Per-object motion (DESIGN.md §2 "Geometry updates", Transforms): the scene stays one flat triangle
+ * soup; an object is a set of its vertices that moves by one 3x4 matrix.  mpt_set_objects sets the
+ * table once: vertex_object[i] in [-1, num_objects) is vertex i's object (-1: static), num_vertices
+ * the scene's count, num_objects >= 1.  The ids and a mask of the vertices the triangles use go to
+ * the device, and the REST POSE is captured: a device-to-device copy of the positions and vertex
+ * normals the context holds at that moment (after any earlier update).  Every later
+ * mpt_update_transforms moves the rest pose, never the previous call's result.
+ * mpt_update_vertices, mpt_update_vertices_device and rebuilds leave the rest pose as captured;
+ * mpt_upload_scene and mpt_upload_scene_mode drop the objects (a new scene).  NULL with
+ * num_objects 0 frees the table, the rest pose and the staging arrays.
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, for a vertex count
+ * other than the scene's, num_objects < 1 with a table, or an id out of range. */
+int mpt_set_objects(MptContext* ctx, const int32_t* vertex_object, int32_t num_vertices, int32_t num_objects);
+/* Moves the objects: matrices is num_objects x 12 floats on the host, per object a row-major 3x4
+ * matrix m applied to the rest pose by a kernel (csrc/xform.h has the arithmetic, shared with
+ * mpt_transform_host byte for byte):
+ *   position  p'[r] = ((m[r][0]*x + m[r][1]*y) + m[r][2]*z) + m[r][3]      (fp32, no fma)
+ *   normal    N n / |N n| with N the cofactor matrix of m's linear part times the sign of its
+ *             determinant (made on the host in double, rounded to float); a normal whose N n has
+ *             a zero or non-finite squared length passes through (the zero normals of vertices
+ *             without has_vertex_normals)
+ * An object whose 12 floats are exactly the identity (1 and +0) and the vertices of object -1 pass
+ * through byte for byte, so an all-identity call changes no bit and reports area_ratio 1.
+ * The context's streams are drained as by mpt_update_vertices; the kernel writes staging arrays
+ * and reduces the largest |coordinate| over the vertices in use and a non-finite flag on the
+ * device; two words are read back; the staging arrays are then swapped in for the positions and
+ * normals, and the refit, the per-triangle attributes, the emissive table and the box pad follow
+ * as in mpt_update_vertices -- with the same bytes as mpt_update_vertices of mpt_transform_host's
+ * output.  No vertex array crosses the bus and the host makes no pass over the vertices.
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, when no objects are
+ * set, num_objects differs from the table's, a matrix entry is not finite (checked on the host) or
+ * a transformed coordinate of any vertex is not finite (the device's flag).  MPT_ERR_HIP part-way
+ * leaves the context without a scene.  The reset rule and info are those of mpt_update_vertices.
+ * The MPT_REFIT_HOST test hook does not apply to this call or to mpt_update_vertices_device: they
+ * always refit on the GPU.  MPT_XFORM_GROUP=1 in the environment (read at the call) makes the
+ * kernels take one vertex per lane instead of four: the same bytes, a measuring aid. */
+int mpt_update_transforms(MptContext* ctx, const float* matrices, int32_t num_objects, MptRefitInfo* info_or_NULL);
+/* mpt_update_vertices for arrays that already live in the memory of the context's device
+ * (3 floats per vertex, any alignment): a kernel first checks the caller's positions (finite, and
+ * the maximum over the vertices in use), so a refusal changes nothing; then device-to-device copies
+ * and the same refit and tables.  The same refusals, and the same bytes afterwards, as
+ * mpt_update_vertices of the same values; a pointer that is not memory of the context's device is
+ * refused with MPT_ERR_INVALID_ARGUMENT.  The reads are enqueued on the context's stream: THE CALLER
+ * GUARANTEES that the arrays are complete with respect to that stream (e.g. by synchronising the
+ * stream that wrote them).  The call returns after the stream is synchronised, so the arrays may
+ * be reused at once. */
+int mpt_update_vertices_device(MptContext* ctx, const float* d_vertices, const float* d_normals_or_NULL,
+                               int32_t num_vertices, MptRefitInfo* info_or_NULL);
+/* No device needed: the host loop of csrc/xform.h -- what mpt_update_transforms writes for a rest
+ * pose, a table and matrices (rest_normals NULL: positions only, out_normals must then be NULL).
+ * MPT_ERR_INVALID_ARGUMENT for a NULL array, an id out of [-1, num_objects), a non-finite matrix
+ * entry or a non-finite output coordinate; the outputs are then unspecified, the inputs untouched. */
+int mpt_transform_host(const float* rest_vertices, const float* rest_normals_or_NULL, const int32_t* vertex_object,
+                       int32_t num_vertices, const float* matrices, int32_t num_objects, float* out_vertices,
+                       float* out_normals_or_NULL);
 /* Downloads a BVH of the context as the kernels read it: which 0 the scene's, 1 the light-hit
  * BVH's (counts of 0 when none is in use).  nodes: 80-byte Node8, tris: 48-byte TriRec records
  * (csrc/bvh8.h; mpt.abi.NODE8_DTYPE / TRIREC_DTYPE).  out_counts (optional): nodes, records,
