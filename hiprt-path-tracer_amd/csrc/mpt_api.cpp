@@ -191,6 +191,13 @@ struct MptContext {
     DBuf<float> rest_pos, rest_nrm, stage_pos, stage_nrm, xf_recs;
     DBuf<uint8_t> vert_used;
     DBuf<uint32_t> xf_red;
+    // skinning (mpt_set_skin, skin.hip): four joint indices and weights per vertex and the joints'
+    // 16-word records.  A skin and an object table exclude each other and share rest_pos /
+    // rest_nrm / stage_pos / stage_nrm: setting one drops the other.
+    int num_joints = -1;                  // -1: no skin set
+    DBuf<int32_t> skin_joints;
+    DBuf<float> skin_weights;
+    DBuf<float4> skin_recs;
     int refit_host_loop = 0;              // test hook (MPT_REFIT_HOST): the refit by the host loop of refit.h
     int light_bvh = 1;                    // MPT_LIGHT_BVH at mpt_create: 0 = one closest-hit traversal per light-hit query
     bool light_bvh_ok = false;            // the light BVH matches the materials (else: the exact closest-hit path)
@@ -1195,10 +1202,13 @@ static int check_scene(const MptScene* s) {
     return MPT_OK;
 }
 
-// The object table of mpt_set_objects, its rest pose and the staging arrays freed.
+// The object table of mpt_set_objects or the skin of mpt_set_skin (at most one of them is set), its
+// rest pose and the staging arrays freed.
 static void drop_objects(MptContext* c) {
     c->num_objects = -1;
+    c->num_joints = -1;
     release_all(c->vert_obj, c->rest_pos, c->rest_nrm, c->stage_pos, c->stage_nrm, c->xf_recs);
+    release_all(c->skin_joints, c->skin_weights, c->skin_recs);
 }
 
 // What a scene upload keeps on the host besides its trees: the box pad, the vertices in use, the
@@ -1212,7 +1222,7 @@ static void take_scene_mirrors(MptContext* c, const MptScene* s) {
     c->h_light_prims.clear();
     c->nodes_light.release();
     c->tris_light.release();
-    drop_objects(c);          // a new scene: the objects and the rest pose were the old one's
+    drop_objects(c);          // a new scene: the objects or the skin and the rest pose were the old one's
     c->vert_used.release();
 }
 
@@ -1439,6 +1449,17 @@ int xform_group() {
     return e && std::atoi(e) == 1 ? 1 : 4;
 }
 
+// the same for k_skin (MPT_SKIN_GROUP=1), and whether it stages a palette that fits in LDS
+// (MPT_SKIN_LDS=0: always the gather through the cache) -- tools/skin_time.py measures all four
+int skin_group() {
+    const char* e = std::getenv("MPT_SKIN_GROUP");
+    return e && std::atoi(e) == 1 ? 1 : 4;
+}
+bool skin_lds() {
+    const char* e = std::getenv("MPT_SKIN_LDS");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
 }  // namespace
 
 int mpt_update_vertices(MptContext* c, const float* vertices, const float* vertex_normals, int32_t num_vertices,
@@ -1471,7 +1492,7 @@ int mpt_set_objects(MptContext* c, const int32_t* vertex_object, int32_t num_ver
     if (!vertex_object) {
         if (num_objects != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
         HIPCHK(hipSetDevice(c->device));
-        drop_objects(c);
+        if (c->num_joints < 0) drop_objects(c);   // (a skin is mpt_set_skin's to free)
         return MPT_OK;
     }
     if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
@@ -1541,6 +1562,88 @@ int mpt_update_transforms(MptContext* c, const float* matrices, int32_t num_obje
     const float pad = std::ldexp(std::max(m, 1.0f), -20);
     c->box_pad = pad;
     return finish_update(c, refit_and_tables(c, pad, nullptr), info, "mpt_update_transforms");
+}
+
+int mpt_set_skin(MptContext* c, const int32_t* joints, const float* weights, int32_t num_vertices, int32_t num_joints) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!joints && !weights) {
+        if (num_joints != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+        HIPCHK(hipSetDevice(c->device));
+        if (c->num_objects < 0) drop_objects(c);   // (an object table is mpt_set_objects' to free)
+        return MPT_OK;
+    }
+    if (!joints || !weights) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
+    if (num_joints < 1) return fail(MPT_ERR_INVALID_ARGUMENT, "skin: bad joint count");
+    if (const char* bad = check_skin_table(joints, weights, (size_t)num_vertices, num_joints)) return fail(MPT_ERR_INVALID_ARGUMENT, bad);
+    HIPCHK(hipSetDevice(c->device));
+    // into new buffers, swapped in when all of them are there: a failure leaves what was set
+    DBuf<int32_t> dj;
+    DBuf<float> dw, rp, rn;
+    hipStream_t st = c->stream;
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = ensure_used_mask(c);
+    if (e == hipSuccess) e = dj.upload(joints, 4 * (size_t)num_vertices, st);
+    if (e == hipSuccess) e = dw.upload(weights, 4 * (size_t)num_vertices, st);
+    if (e == hipSuccess) e = rp.alloc(c->pos.n);
+    if (e == hipSuccess) e = rn.alloc(c->nrm.n);
+    if (e == hipSuccess) e = hipMemcpyAsync(rp.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rn.p, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_skin: ") + hipGetErrorString(e));
+    }
+    drop_objects(c);
+    std::swap(c->skin_joints.p, dj.p); std::swap(c->skin_joints.n, dj.n);
+    std::swap(c->skin_weights.p, dw.p); std::swap(c->skin_weights.n, dw.n);
+    std::swap(c->rest_pos.p, rp.p); std::swap(c->rest_pos.n, rp.n);
+    std::swap(c->rest_nrm.p, rn.p); std::swap(c->rest_nrm.n, rn.n);
+    c->num_joints = num_joints;
+    return MPT_OK;
+}
+
+int mpt_update_skin(MptContext* c, const float* joint_matrices, int32_t num_joints, MptRefitInfo* info) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!joint_matrices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (c->num_joints < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no skin set");
+    if (num_joints != c->num_joints) return fail(MPT_ERR_INVALID_ARGUMENT, "joint count differs from the table's");
+    if (!matrices_finite(joint_matrices, num_joints)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite matrix entry");
+    if (c->rest_pos.n != c->pos.n || c->rest_nrm.n != c->nrm.n || 3 * c->skin_joints.n != 4 * c->pos.n ||
+        c->skin_weights.n != c->skin_joints.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "skin does not fit the scene");
+    std::vector<float4> recs;
+    make_skin_records(joint_matrices, num_joints, recs);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    float m = 0.0f;
+    bool bad = false;
+    // everything up to the swap writes scratch only: a refusal or an error here changes nothing
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = ensure_used_mask(c);
+    if (e == hipSuccess) e = c->stage_pos.alloc(c->pos.n);
+    if (e == hipSuccess) e = c->stage_nrm.alloc(c->nrm.n);
+    if (e == hipSuccess) e = c->xf_red.alloc(2);
+    if (e == hipSuccess) e = c->skin_recs.upload(recs.data(), recs.size(), st);
+    if (e == hipSuccess)
+        e = launch_skin(c->rest_pos.p, c->rest_nrm.p, c->skin_joints.p, c->skin_weights.p, c->vert_used.p,
+                        (const float*)c->skin_recs.p, num_joints, (int)(c->pos.n / 3), c->stage_pos.p, c->stage_nrm.p, c->xf_red.p,
+                        skin_group(), skin_lds(), st);
+    if (e == hipSuccess) e = read_reduction(c, &m, &bad);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->has_scene = false;
+        return fail(MPT_ERR_HIP, std::string("mpt_update_skin: ") + hipGetErrorString(e));
+    }
+    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
+    std::swap(c->pos.p, c->stage_pos.p);
+    std::swap(c->nrm.p, c->stage_nrm.p);
+    const float pad = std::ldexp(std::max(m, 1.0f), -20);
+    c->box_pad = pad;
+    return finish_update(c, refit_and_tables(c, pad, nullptr), info, "mpt_update_skin");
 }
 
 int mpt_update_vertices_device(MptContext* c, const float* d_vertices, const float* d_normals, int32_t num_vertices,

@@ -429,6 +429,19 @@ bool transform_host(const float* rest_pos, const float* rest_nrm, const int32_t*
                     float* out_nrm);
 bool matrices_finite(const float* matrices, int32_t num_objects);
 void make_xform_records(const float* matrices, int32_t num_objects, std::vector<float>& recs);
+// skin.hip (skin.h): n rest-pose vertices skinned by four weighted joints each (joints, weights: 4
+// entries per vertex; recs: num_joints 16-word records, 16-byte aligned) into out_pos / out_nrm;
+// red and group as launch_xform.  lds: copy the palette into LDS once per block when it has at most
+// MPT_SKIN_LDS_JOINTS records (else, and with lds false, gather it through the cache).
+hipError_t launch_skin(const float* rest_pos, const float* rest_nrm, const int32_t* joints, const float* weights,
+                       const uint8_t* used, const float* recs, int num_joints, int n, float* out_pos, float* out_nrm,
+                       uint32_t* red, int group, bool lds, hipStream_t st);
+// the host loop of the same arithmetic (false: a non-finite output coordinate); the table's check
+// (NULL, or what is wrong with it) and the records (12 floats per joint -> 16 words) both paths share
+bool skin_host(const float* rest_pos, const float* rest_nrm, const int32_t* joints, const float* weights, size_t n,
+               const float* recs, float* out_pos, float* out_nrm);
+const char* check_skin_table(const int32_t* joints, const float* weights, size_t num_vertices, int32_t num_joints);
+void make_skin_records(const float* matrices, int32_t num_joints, std::vector<float4>& recs);
 // the scene BVH as mpt_upload_scene builds it (rebuilt shallower while too deep for stack_limit
 // entries); returns the stack limit in force (MPT_BVH_MAX_STACK)
 int build_scene_bvh8(const float* vertices, const int32_t* indices, int32_t num_triangles, BVH8& out, int stack_limit);

@@ -158,6 +158,15 @@ void GPURenderer::update_transforms(const float* matrices, int32_t num_objects, 
     reset();   // as update_vertices: what was accumulated shows the old geometry
 }
 
+void GPURenderer::set_skin(const int32_t* joints, const float* weights, int32_t num_vertices, int32_t num_joints) {
+    for (MptContext* c : m_ctxs) check(mpt_set_skin(c, joints, weights, num_vertices, num_joints));
+}
+
+void GPURenderer::update_skin(const float* joint_matrices, int32_t num_joints, MptRefitInfo* info) {
+    for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_update_skin(m_ctxs[k], joint_matrices, num_joints, k == 0 ? info : nullptr));
+    reset();   // as update_vertices: what was accumulated shows the old geometry
+}
+
 void GPURenderer::rebuild_bvh(MptRebuildInfo* info, int32_t mode) {
     for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_rebuild_bvh_mode(m_ctxs[k], mode, k == 0 ? info : nullptr));
     // (no reset: results do not depend on the tree)

@@ -140,6 +140,15 @@ public:
     // update_vertices.  info (optional): the first context's report.
     void set_objects(const int32_t* vertex_object, int32_t num_vertices, int32_t num_objects);
     void update_transforms(const float* matrices, int32_t num_objects, MptRefitInfo* info = nullptr);
+    // set_skin / update_skin (no counterpart in the reference): linear-blend skinning of the flat
+    // scene.  set_skin gives every context four joint indices and weights per vertex (all weights
+    // zero: not skinned; NULL tables with 0 joints remove the skin) and captures the rest pose on
+    // its GPU (mpt_set_skin); a skin and the objects of set_objects exclude each other, setting one
+    // drops the other.  update_skin blends one row-major 3x4 matrix per joint for every vertex of
+    // the rest pose on every context's GPU and refits its BVHs (mpt_update_skin).  The accumulation
+    // restarts as after update_vertices.  info (optional): the first context's report.
+    void set_skin(const int32_t* joints, const float* weights, int32_t num_vertices, int32_t num_joints);
+    void update_skin(const float* joint_matrices, int32_t num_joints, MptRefitInfo* info = nullptr);
     // rebuild_bvh (no counterpart in the reference): every context rebuilds its BVHs on its GPU
     // from the positions it holds (mpt_rebuild_bvh_mode), e.g. once update_vertices reports a large
     // area_ratio.  The accumulation continues: traversal results do not depend on the tree.

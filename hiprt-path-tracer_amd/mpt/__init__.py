@@ -22,7 +22,8 @@ from . import scene
 from ._build import LIB_PATH
 
 __all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
-           "display_host", "write_png", "denoise_host", "bvh_refit_host", "bvh_build_host", "transform_host"]
+           "display_host", "write_png", "denoise_host", "bvh_refit_host", "bvh_build_host", "transform_host", "skin_host",
+           "SKIN_LDS_JOINTS"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -38,7 +39,10 @@ SYMBOLS = [
     "mpt_update_vertices", "mpt_get_bvh", "mpt_bvh_refit_host", "mpt_rebuild_bvh", "mpt_bvh_build_host",
     "mpt_rebuild_bvh_mode", "mpt_bvh_build_host_mode", "mpt_upload_scene_mode",
     "mpt_set_objects", "mpt_update_transforms", "mpt_update_vertices_device", "mpt_transform_host",
+    "mpt_set_skin", "mpt_update_skin", "mpt_skin_host",
 ]
+
+SKIN_LDS_JOINTS = abi.SKIN_LDS_JOINTS
 
 
 class MptError(RuntimeError):
@@ -129,6 +133,9 @@ def lib() -> C.CDLL:
     L.mpt_update_transforms.argtypes = [vp, vp, i32, C.POINTER(abi.RefitInfo)]
     L.mpt_update_vertices_device.argtypes = [vp, vp, vp, i32, C.POINTER(abi.RefitInfo)]
     L.mpt_transform_host.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
+    L.mpt_set_skin.argtypes = [vp, vp, vp, i32, i32]
+    L.mpt_update_skin.argtypes = [vp, vp, i32, C.POINTER(abi.RefitInfo)]
+    L.mpt_skin_host.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp]
     _lib = L
     return L
 
@@ -355,6 +362,35 @@ def transform_host(rest_vertices, rest_normals, vertex_object, matrices):
     return ov, on
 
 
+def _skin_table(joints, weights, who):
+    """[V, 4] joint indices and weights -> contiguous int32 and float32 arrays."""
+    j = np.ascontiguousarray(joints, np.int32)
+    w = np.ascontiguousarray(weights, np.float32)
+    if j.ndim != 2 or j.shape[1] != 4 or w.shape != j.shape:
+        raise ValueError(f"{who}: joints of shape {j.shape} and weights of shape {w.shape}, not both [V, 4]")
+    return j, w
+
+
+def skin_host(rest_vertices, rest_normals, joints, weights, matrices):
+    """mpt_skin_host, no GPU: the host loop of csrc/skin.h -- the positions ([V, 3] float32) and,
+    when rest_normals is given, the vertex normals that GPURenderer.update_skin(matrices) leaves on
+    the device for this rest pose and skin (joints: int32 [V, 4] into the palette, weights: float32
+    [V, 4], all zero for a vertex that is not skinned; matrices: [J, 3, 4] or [J, 4, 4]).  Returns
+    (vertices, normals or None)."""
+    v = np.ascontiguousarray(rest_vertices, np.float32).reshape(-1, 3)
+    n = None if rest_normals is None else np.ascontiguousarray(rest_normals, np.float32).reshape(-1, 3)
+    if n is not None and n.shape != v.shape:
+        raise ValueError(f"skin_host: {n.shape[0]} normals for {v.shape[0]} vertices")
+    j, w = _skin_table(joints, weights, "skin_host")
+    if len(j) != len(v):
+        raise ValueError(f"skin_host: {len(j)} rows of joints for {len(v)} vertices")
+    m = _matrices(matrices, "skin_host")
+    ov = np.empty_like(v)
+    on = None if n is None else np.empty_like(n)
+    _check(lib().mpt_skin_host(_p(v), _p(n), _p(j), _p(w), len(v), _p(m), len(m), _p(ov), _p(on)))
+    return ov, on
+
+
 def _on_device(a):
     """A torch tensor in GPU memory (anything else, a CPU tensor included, is a host array)."""
     return bool(getattr(a, "is_cuda", False))
@@ -457,6 +493,29 @@ class GPURenderer:
         m = _matrices(matrices, "update_transforms")
         ri = abi.RefitInfo() if info else None
         _check(lib().mpt_update_transforms(self.h, _p(m), len(m), C.byref(ri) if info else None))
+        return ri
+
+    def set_skin(self, joints, weights=None, num_joints=None):
+        """mpt_set_skin: joints is int32 [V, 4], per vertex of the scene four indices into a palette
+        of num_joints joints (None: the largest index + 1), weights float32 [V, 4] (all zero: the
+        vertex is not skinned).  Captures the rest pose -- the positions and normals on the device
+        now -- which every update_skin poses.  A skin and the objects of set_objects exclude each
+        other: setting one drops the other.  joints=None removes the skin."""
+        if joints is None:
+            _check(lib().mpt_set_skin(self.h, None, None, 0, 0))
+            return
+        j, w = _skin_table(joints, weights, "set_skin")
+        k = int(j.max()) + 1 if num_joints is None else int(num_joints)
+        _check(lib().mpt_set_skin(self.h, _p(j), _p(w), len(j), k))
+
+    def update_skin(self, matrices, info=False):
+        """mpt_update_skin: one matrix per joint ([J, 3, 4], or [J, 4, 4] whose bottom row is
+        dropped), relative to the pose at set_skin, blended per vertex and applied to the rest pose
+        on the GPU, then the refit of both BVHs: 64 bytes per joint cross the bus, no vertex array.
+        The next frame must carry need_to_reset.  info=True returns the abi.RefitInfo, else None."""
+        m = _matrices(matrices, "update_skin")
+        ri = abi.RefitInfo() if info else None
+        _check(lib().mpt_update_skin(self.h, _p(m), len(m), C.byref(ri) if info else None))
         return ri
 
     def rebuild_bvh(self, info=False, mode=abi.BUILD_LBVH):

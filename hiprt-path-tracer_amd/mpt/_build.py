@@ -19,7 +19,7 @@ INCLUDE = ROOT.parent / "include"
 LIB_PATH = PKG_DIR / "libmpt.so"
 OBJ_DIR = CSRC / "build"
 
-SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp", "display.hip", "denoise.hip", "refit.hip", "lbvh.hip", "ploc.hip", "sah.hip", "upload.hip", "xform.hip"]
+SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp", "display.hip", "denoise.hip", "refit.hip", "lbvh.hip", "ploc.hip", "sah.hip", "upload.hip", "xform.hip", "skin.hip"]
 # mpt_part.hip is compiled once per part (-DMPT_TU_PART=k): the shading and ReSTIR DI kernel
 # instantiations, so that they compile in parallel with the rest
 PARTS = [1, 2, 3, 4, 5, 6, 7]
@@ -99,6 +99,9 @@ UPLOAD_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" /
 # GPURenderer::set_objects / update_transforms over several contexts (tests/test_xform_host_cpp.py)
 XFORM_TEST = HOST_DIR / "xform_move"
 XFORM_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "xform_move.cpp"]
+# GPURenderer::set_skin / update_skin over several contexts (tests/test_skin_host_cpp.py)
+SKIN_TEST = HOST_DIR / "skin_move"
+SKIN_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "skin_move.cpp"]
 
 
 def _build_driver(exe: Path, sources, lib: Path, verbose: bool) -> Path:
@@ -122,7 +125,7 @@ def build_host_test(verbose: bool = True) -> Path:
     """The C++ GPURenderer mirror (host/) linked with libmpt into the test drivers of
     tests/test_host_cpp.py, tests/test_display_host_cpp.py, tests/test_denoise_host_cpp.py and
     tests/test_refit_host_cpp.py, tests/test_rebuild_host_cpp.py, tests/test_ploc_host_cpp.py,
-    tests/test_upload_host_cpp.py, tests/test_xform_host_cpp.py
+    tests/test_upload_host_cpp.py, tests/test_xform_host_cpp.py, tests/test_skin_host_cpp.py
     (plain g++: the host side is ordinary C++ over the C ABI)."""
     lib = build(verbose=verbose)
     _build_driver(DENOISE_TEST, DENOISE_SOURCES, lib, verbose)
@@ -132,6 +135,7 @@ def build_host_test(verbose: bool = True) -> Path:
     _build_driver(PLOC_TEST, PLOC_SOURCES, lib, verbose)
     _build_driver(UPLOAD_TEST, UPLOAD_SOURCES, lib, verbose)
     _build_driver(XFORM_TEST, XFORM_SOURCES, lib, verbose)
+    _build_driver(SKIN_TEST, SKIN_SOURCES, lib, verbose)
     return _build_driver(HOST_TEST, HOST_SOURCES, lib, verbose)
 
 

@@ -52,6 +52,49 @@ _NCOMP = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
 DATA_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "data")
 
 
+class SkinData:
+    """The skin of a glTF file's skinned mesh nodes over SceneData's flat vertices: what
+    GPURenderer.set_skin takes, and what skin_matrices needs to pose it."""
+
+    def __init__(self):
+        self.joints = None        # int32 [V, 4] into the palette
+        self.weights = None       # float32 [V, 4]; all zero for the vertices of unskinned meshes
+        self.joint_nodes = None   # int32 [J]: the node of every palette entry (the skins of the
+        #                           skinned mesh nodes, concatenated in node order)
+        self.bind = None          # float64 [J, 4, 4]: inverse_bind_j @ inverse(world of the mesh node) --
+        #                           SceneData.vertices are in world space, whereas glTF skins the
+        #                           mesh's own coordinates and ignores the skinned node's transform
+        self.node_parents = None  # int32 [N]: every node's parent, -1 for a root
+        self.node_locals = None   # float64 [N, 4, 4]: every node's local matrix in the file
+
+    @property
+    def num_joints(self):
+        return len(self.joint_nodes)
+
+
+def skin_matrices(sd, node_locals=None):
+    """The joint matrices of a pose for GPURenderer.update_skin / mpt.skin_host: float32 [J, 3, 4],
+    global_j @ sd.skin.bind[j], the global joint transforms recomputed in float64 from the file's
+    node-local matrices with those in node_locals ({node index: 4x4}) put in their place (None:
+    the file's own pose)."""
+    sk = sd.skin
+    if sk is None:
+        raise ValueError("skin_matrices: the scene has no skin")
+    loc = sk.node_locals.copy()
+    for ni, m in (node_locals or {}).items():
+        loc[ni] = np.asarray(m, np.float64).reshape(4, 4)
+    glob = {}
+
+    def world_of(ni):
+        if ni not in glob:
+            pa = int(sk.node_parents[ni])
+            glob[ni] = loc[ni] if pa < 0 else world_of(pa) @ loc[ni]
+        return glob[ni]
+
+    out = np.stack([world_of(int(ni)) @ sk.bind[k] for k, ni in enumerate(sk.joint_nodes)])
+    return np.ascontiguousarray(out[:, :3, :], np.float32)
+
+
 class SceneData:
     """Flat arrays + materials, i.e. what ``mpt_upload_scene`` receives."""
 
@@ -67,6 +110,7 @@ class SceneData:
         self.textures = []            # list of uint8 [h, w, 4]
         self.camera_info = None       # dict for make_camera
         self.vertex_object = None     # int32 [V] or None: per vertex the ordinal of its mesh node (glTF loader)
+        self.skin = None              # SkinData or None: the file's skinned mesh nodes (glTF loader)
         self.name = ""
 
     @property
@@ -389,6 +433,7 @@ def load_gltf(path, aspect_override=None):
     inst = []
     need_default = False
     n_mesh_nodes = 0
+    pal_nodes, pal_bind = [], []     # SceneData.skin: the palette, one stretch per skinned mesh node
     for ni, n in enumerate(g["nodes"]):
         if "mesh" not in n or ni not in world:
             continue
@@ -397,6 +442,18 @@ def load_gltf(path, aspect_override=None):
         M = world[ni]
         R = M[:3, :3]
         RIT = np.linalg.inv(R).T
+        pal0 = None
+        if "skin" in n:
+            sk = g["skins"][n["skin"]]
+            pal0 = len(pal_nodes)
+            if "inverseBindMatrices" in sk:   # column-major MAT4
+                ibm = _accessor(g, bins, sk["inverseBindMatrices"]).astype(np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)
+            else:
+                ibm = np.tile(np.eye(4), (len(sk["joints"]), 1, 1))
+            Minv = np.linalg.inv(M)
+            for k, jn in enumerate(sk["joints"]):
+                pal_nodes.append(jn)
+                pal_bind.append(ibm[k] @ Minv)
         for prim in g["meshes"][n["mesh"]]["primitives"]:
             mode = prim.get("mode", 4)
             if mode not in (4, 5, 6):
@@ -421,7 +478,19 @@ def load_gltf(path, aspect_override=None):
             if mi is None:
                 need_default = True
                 mi = n_mat
-            inst.append((mi, pos, nrm, uv, _triangles(mode, idx), node_ord))
+            infl = None
+            if pal0 is not None and "JOINTS_0" in att and "WEIGHTS_0" in att:
+                if "JOINTS_1" in att or "WEIGHTS_1" in att:
+                    raise ValueError(f"{os.path.basename(path)}: mesh {n['mesh']}: more than four joint influences per "
+                                     "vertex (JOINTS_1) are not supported")
+                wgt = _accessor(g, bins, att["WEIGHTS_0"])
+                if wgt.dtype != np.float32:      # an integer accessor without the normalized flag
+                    wgt = wgt.astype(np.float32) / np.float32(_NORM[wgt.dtype])
+                jnt = _accessor(g, bins, att["JOINTS_0"]).astype(np.int64)
+                if jnt.min() < 0 or jnt.max() >= len(pal_nodes) - pal0:
+                    raise ValueError(f"{os.path.basename(path)}: mesh {n['mesh']}: joint index outside its skin")
+                infl = ((jnt + pal0).astype(np.int32), wgt.astype(np.float32))
+            inst.append((mi, pos, nrm, uv, _triangles(mode, idx), node_ord, infl))
 
     total_mats = n_mat + (1 if need_default else 0)
     tex_idx, const_em, textures, tex_count = _load_textures(g, bins, base, materials_json)
@@ -435,11 +504,11 @@ def load_gltf(path, aspect_override=None):
 
     sd = SceneData()
     sd.name = os.path.splitext(os.path.basename(path))[0]
-    tri, verts, nrms, hasn, uvs, mids, vobj = [], [], [], [], [], [], []
+    tri, verts, nrms, hasn, uvs, mids, vobj, vjnt, vwgt = [], [], [], [], [], [], [], [], []
     voff = 0
     # PreTransformVertices: output meshes ordered by material index
     for mi in range(total_mats):
-        for (m, pos, nrm, uv, idx, node_ord) in inst:
+        for (m, pos, nrm, uv, idx, node_ord, infl) in inst:
             if m != mi:
                 continue
             tri.append(idx + voff)
@@ -454,6 +523,8 @@ def load_gltf(path, aspect_override=None):
                 uvs.append(np.zeros((len(pos), 2), np.float32))
             mids.append(np.full(len(idx), mi, np.int32))
             vobj.append(np.full(len(pos), node_ord, np.int32))
+            vjnt.append(infl[0] if infl else np.zeros((len(pos), 4), np.int32))
+            vwgt.append(infl[1] if infl else np.zeros((len(pos), 4), np.float32))
             voff += len(pos)
     sd.triangle_indices = np.concatenate(tri).astype(np.int32).ravel()
     sd.vertices = np.concatenate(verts).astype(np.float32)
@@ -462,6 +533,18 @@ def load_gltf(path, aspect_override=None):
     sd.texcoords = np.concatenate(uvs)
     sd.material_indices = np.concatenate(mids)
     sd.vertex_object = np.concatenate(vobj)
+    if pal_nodes:
+        sk = SkinData()
+        sk.joints = np.ascontiguousarray(np.concatenate(vjnt), np.int32)
+        sk.weights = np.ascontiguousarray(np.concatenate(vwgt), np.float32)
+        sk.joint_nodes = np.array(pal_nodes, np.int32)
+        sk.bind = np.stack(pal_bind)
+        sk.node_parents = np.full(len(g["nodes"]), -1, np.int32)
+        for ni, nd in enumerate(g["nodes"]):
+            for c in nd.get("children", []):
+                sk.node_parents[c] = ni
+        sk.node_locals = np.stack([_node_matrix(nd) for nd in g["nodes"]])
+        sd.skin = sk
     sd.materials = mats
     sd.textures = textures
 

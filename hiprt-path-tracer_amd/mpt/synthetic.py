@@ -726,3 +726,114 @@ def procedural_city_textured(seed: int = 1235, tex_scale: float = 3.0) -> SceneD
     sd.textures = textures
     sd.name = f"procedural_city_textured_{seed}"
     return sd.finalize()
+
+
+# ---- a skinned asset (no skinned glTF file ships with the project) --------------------------------
+def write_skinned_gltf(path: str, rings: int = 7, sides: int = 8, joints: int = 3, length: float = 1.8,
+                       radius: float = 0.25, normalized_weights: bool = True) -> str:
+    """Writes a small skinned glTF 2 scene to path (.gltf, buffers embedded) and returns path.
+
+    * node 0: a tube of `rings` rings of `sides` vertices along its own y axis, bound to a chain of
+      `joints` (2 or 3) joints that divide its length; a vertex between two segment centres blends
+      the two joints linearly by height (JOINTS_0 as unsigned bytes, WEIGHTS_0 as normalised
+      unsigned shorts that sum to 65535, or as floats).  The node carries a rotation and a
+      translation of its own, which glTF ignores for a skinned mesh: the inverse bind matrices are
+      inverse(global_j) @ world(node 0), so the file's pose shows the tube where that transform puts it.
+    * nodes 1 .. joints: the chain, the root placed by a matrix, each child one segment up its
+      parent's y axis.
+    * then an unskinned floor quad with an emissive strip (a second mesh, two materials) and a camera."""
+    import base64
+    import json
+
+    if joints not in (2, 3) or rings < 2 or sides < 3:
+        raise ValueError("write_skinned_gltf: joints must be 2 or 3, rings >= 2, sides >= 3")
+    ys = np.linspace(0.0, length, rings)
+    ang = np.arange(sides) * (2.0 * np.pi / sides)
+    ring = np.stack([np.cos(ang), np.zeros(sides), np.sin(ang)], 1)
+    P = np.concatenate([ring * radius + [0.0, y, 0.0] for y in ys]).astype(np.float32)
+    N = np.tile(ring, (rings, 1)).astype(np.float32)
+    I = []
+    for r in range(rings - 1):
+        for s in range(sides):
+            a, b = r * sides + s, r * sides + (s + 1) % sides
+            I += [a, a + sides, b, b, a + sides, b + sides]
+    I = np.array(I, np.uint16)
+    seg = length / joints
+    t = np.repeat(ys, sides) / seg - 0.5
+    ja = np.clip(np.floor(t), 0, joints - 2).astype(np.int64)
+    f = np.clip(t - ja, 0.0, 1.0)
+    J = np.zeros((len(P), 4), np.uint8)
+    J[:, 0], J[:, 1] = ja, ja + 1
+    if normalized_weights:
+        Wt = np.zeros((len(P), 4), np.uint16)
+        Wt[:, 1] = np.round(f * 65535.0)
+        Wt[:, 0] = 65535 - Wt[:, 1]
+    else:
+        Wt = np.zeros((len(P), 4), np.float32)
+        Wt[:, 1] = f
+        Wt[:, 0] = np.float32(1.0) - Wt[:, 1]
+
+    c, s = math.cos(math.radians(25.0)), math.sin(math.radians(25.0))
+    W = np.array([[c, -s, 0.0, -0.4], [s, c, 0.0, 0.1], [0.0, 0.0, 1.0, -0.2], [0.0, 0.0, 0.0, 1.0]])
+    glob, up = [W.copy()], np.eye(4)
+    up[1, 3] = seg
+    for _ in range(joints - 1):
+        glob.append(glob[-1] @ up)
+    ibm = np.stack([np.linalg.inv(G) @ W for G in glob]).astype(np.float32)
+
+    FP = np.array([[-2, 0, 2], [2, 0, 2], [2, 0, -2], [-2, 0, -2], [-0.5, 2.5, 0.5], [0.5, 2.5, 0.5], [0.5, 2.5, -0.5],
+                   [-0.5, 2.5, -0.5]], np.float32)
+    FN = np.array([[0, 1, 0]] * 4 + [[0, -1, 0]] * 4, np.float32)
+
+    chunks, views, accessors = [], [], []
+
+    def acc(arr, ctype, typ, normalized=False):
+        arr = np.ascontiguousarray(arr)
+        off = sum(len(b) for b in chunks)
+        chunks.append(arr.tobytes() + b"\0" * ((-arr.nbytes) % 4))
+        views.append({"buffer": 0, "byteOffset": off, "byteLength": arr.nbytes})
+        a = {"bufferView": len(views) - 1, "componentType": ctype, "count": int(arr.shape[0]), "type": typ}
+        if normalized:
+            a["normalized"] = True
+        if typ == "VEC3":
+            a["min"], a["max"] = arr.min(0).tolist(), arr.max(0).tolist()
+        accessors.append(a)
+        return len(accessors) - 1
+
+    tube = {"attributes": {"POSITION": acc(P, 5126, "VEC3"), "NORMAL": acc(N, 5126, "VEC3"), "JOINTS_0": acc(J, 5121, "VEC4"),
+                           "WEIGHTS_0": acc(Wt, 5123 if normalized_weights else 5126, "VEC4", normalized_weights)},
+            "indices": acc(I, 5123, "SCALAR"), "material": 0}
+    fl_p, fl_n = acc(FP, 5126, "VEC3"), acc(FN, 5126, "VEC3")
+    floor = [{"attributes": {"POSITION": fl_p, "NORMAL": fl_n}, "indices": acc(np.array([0, 1, 2, 0, 2, 3], np.uint16), 5123, "SCALAR"),
+              "material": 1},
+             {"attributes": {"POSITION": fl_p, "NORMAL": fl_n}, "indices": acc(np.array([4, 6, 5, 4, 7, 6], np.uint16), 5123, "SCALAR"),
+              "material": 2}]
+    # the transposed ibm, flattened row by row, is glTF's column-major MAT4
+    skin = {"joints": list(range(1, joints + 1)),
+            "inverseBindMatrices": acc(ibm.transpose(0, 2, 1).reshape(-1, 16), 5126, "MAT4")}
+    nodes = [{"mesh": 0, "skin": 0, "rotation": [0.0, 0.0, math.sin(math.radians(12.5)), math.cos(math.radians(12.5))],
+              "translation": [-0.4, 0.1, -0.2]},
+             {"matrix": W.T.reshape(-1).tolist(), "children": [2]}]
+    for k in range(2, joints + 1):
+        nd = {"translation": [0.0, seg, 0.0]}
+        if k < joints:
+            nd["children"] = [k + 1]
+        nodes.append(nd)
+    nodes.append({"mesh": 1})
+    nodes.append({"camera": 0, "translation": [0.0, 1.0, 4.0]})
+    materials = [
+        {"name": "tube", "pbrMetallicRoughness": {"baseColorFactor": [0.7, 0.4, 0.3, 1.0], "metallicFactor": 0.0, "roughnessFactor": 0.6}},
+        {"name": "floor", "pbrMetallicRoughness": {"baseColorFactor": [0.6, 0.6, 0.6, 1.0], "metallicFactor": 0.0, "roughnessFactor": 0.9}},
+        {"name": "light", "pbrMetallicRoughness": {"baseColorFactor": [1, 1, 1, 1], "metallicFactor": 0.0},
+         "emissiveFactor": [1.0, 1.0, 1.0], "extensions": {"KHR_materials_emissive_strength": {"emissiveStrength": 8.0}}},
+    ]
+    binary = b"".join(chunks)
+    g = {"asset": {"version": "2.0"}, "scene": 0, "scenes": [{"nodes": [0, 1, joints + 1, joints + 2]}], "nodes": nodes,
+         "meshes": [{"primitives": [tube]}, {"primitives": floor}], "skins": [skin], "materials": materials,
+         "accessors": accessors, "bufferViews": views,
+         "buffers": [{"byteLength": len(binary), "uri": "data:application/octet-stream;base64," + base64.b64encode(binary).decode()}],
+         "cameras": [{"type": "perspective", "perspective": {"yfov": 0.75, "aspectRatio": 1.0, "znear": 0.05, "zfar": 50.0}}],
+         "extensionsUsed": ["KHR_materials_emissive_strength"]}
+    with open(path, "w") as f:
+        json.dump(g, f)
+    return path

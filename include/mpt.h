@@ -603,7 +603,8 @@ int mpt_update_vertices(MptContext* ctx, const float* vertices, const float* ver
  * mpt_update_transforms moves the rest pose, never the previous call's result.
  * mpt_update_vertices, mpt_update_vertices_device and rebuilds leave the rest pose as captured;
  * mpt_upload_scene and mpt_upload_scene_mode drop the objects (a new scene).  NULL with
- * num_objects 0 frees the table, the rest pose and the staging arrays.
+ * num_objects 0 frees the table, the rest pose and the staging arrays.  A skin (mpt_set_skin)
+ * and an object table exclude each other: setting the table drops a skin.
  * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, for a vertex count
  * other than the scene's, num_objects < 1 with a table, or an id out of range. */
 int mpt_set_objects(MptContext* ctx, const int32_t* vertex_object, int32_t num_vertices, int32_t num_objects);
@@ -649,6 +650,58 @@ int mpt_update_vertices_device(MptContext* ctx, const float* d_vertices, const f
 int mpt_transform_host(const float* rest_vertices, const float* rest_normals_or_NULL, const int32_t* vertex_object,
                        int32_t num_vertices, const float* matrices, int32_t num_objects, float* out_vertices,
                        float* out_normals_or_NULL);
+/* Skinning (DESIGN.md §2 "Geometry updates", Skinning): linear-blend skinning of the flat scene, the
+ * general case of which an object of mpt_set_objects is the one-joint, weight-1 instance.
+ * mpt_set_skin sets the table once: joints and weights hold num_vertices x 4 entries, per vertex
+ * four indices into a palette of num_joints >= 1 joints and their four weights (all four zero: the
+ * vertex is not skinned).  The tables and a mask of the vertices the triangles use go to the
+ * device, and the REST POSE is captured exactly as by mpt_set_objects.  Every later
+ * mpt_update_skin skins the rest pose, never the previous call's result.
+ * A skin and an object table exclude each other and share the rest pose and the staging arrays:
+ * mpt_set_skin drops an object table and mpt_set_objects drops a skin; mpt_upload_scene and
+ * mpt_upload_scene_mode drop either.  mpt_update_vertices, mpt_update_vertices_device and rebuilds
+ * leave the rest pose as captured.  NULL tables with num_joints 0 free the skin, the rest pose and
+ * the staging arrays (and leave an object table alone, as mpt_set_objects(NULL) leaves a skin).
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, for a vertex count
+ * other than the scene's, num_joints < 1 with a table, an index outside [0, num_joints) in any slot
+ * (whatever its weight) or a weight that is not finite. */
+int mpt_set_skin(MptContext* ctx, const int32_t* joints, const float* weights, int32_t num_vertices, int32_t num_joints);
+/* The most joints whose records (64 bytes each) mpt_update_skin's kernel stages in LDS; a larger
+ * palette is gathered through the cache.  Both give the same bytes. */
+#define MPT_SKIN_LDS_JOINTS 256
+/* Poses the skin: joint_matrices is num_joints x 12 floats on the host, per joint a row-major 3x4
+ * matrix M_j relative to the pose at mpt_set_skin, applied to the rest pose by a kernel
+ * (csrc/skin.h has the arithmetic, shared with mpt_skin_host byte for byte; fp32, no fma):
+ *   blend     B[e] = ((w0*M_j0[e] + w1*M_j1[e]) + w2*M_j2[e]) + w3*M_j3[e], the 12 entries e
+ *   position  p'[r] = ((B[r][0]*x + B[r][1]*y) + B[r][2]*z) + B[r][3]
+ *   normal    N n / |N n| with N the cofactor matrix of B's linear part times the sign of its
+ *             determinant, computed per vertex in fp32 (each cofactor a*b - c*d with two rounded
+ *             products, the determinant (a00*c00 + a01*c01) + a02*c02); a zero or non-finite
+ *             squared length passes the rest normal through
+ * A vertex passes through byte for byte when its four weights are all zero or when every joint with
+ * a non-zero weight has exactly the identity matrix (1 and +0), so an all-identity pose changes no
+ * bit and reports area_ratio 1, whatever the weights sum to.
+ * The flow is mpt_update_transforms': streams drained, 64 bytes per joint uploaded, the kernel
+ * writes staging arrays and reduces the largest |coordinate| over the vertices in use and a
+ * non-finite flag, two words are read back, the staging arrays are swapped in, and the refit, the
+ * per-triangle attributes, the emissive table and the box pad follow -- with the same bytes as
+ * mpt_update_vertices of mpt_skin_host's output.
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, when no skin is
+ * set, num_joints differs from the table's, a matrix entry is not finite (checked on the host) or a
+ * skinned coordinate of any vertex is not finite (the device's flag).  MPT_ERR_HIP part-way leaves
+ * the context without a scene.  The reset rule and info are those of mpt_update_vertices; the refit
+ * is always the GPU's.  Measuring aids, read from the environment at the call, the same bytes:
+ * MPT_SKIN_GROUP=1 takes one vertex per lane instead of four, MPT_SKIN_LDS=0 gathers the palette
+ * through the cache whatever its size. */
+int mpt_update_skin(MptContext* ctx, const float* joint_matrices, int32_t num_joints, MptRefitInfo* info_or_NULL);
+/* No device needed: the host loop of csrc/skin.h -- what mpt_update_skin writes for a rest pose,
+ * tables and matrices (rest_normals NULL: positions only, out_normals must then be NULL).
+ * MPT_ERR_INVALID_ARGUMENT for a NULL array, num_joints < 1, an index outside [0, num_joints) in
+ * any slot, a non-finite weight or matrix entry, or a non-finite output coordinate; the outputs are
+ * then unspecified, the inputs untouched. */
+int mpt_skin_host(const float* rest_vertices, const float* rest_normals_or_NULL, const int32_t* joints, const float* weights,
+                  int32_t num_vertices, const float* joint_matrices, int32_t num_joints, float* out_vertices,
+                  float* out_normals_or_NULL);
 /* Downloads a BVH of the context as the kernels read it: which 0 the scene's, 1 the light-hit
  * BVH's (counts of 0 when none is in use).  nodes: 80-byte Node8, tris: 48-byte TriRec records
  * (csrc/bvh8.h; mpt.abi.NODE8_DTYPE / TRIREC_DTYPE).  out_counts (optional): nodes, records,
