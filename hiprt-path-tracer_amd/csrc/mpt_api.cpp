@@ -19,6 +19,7 @@
 #include "bvh8.h"
 #include "denoise.h"
 #include "display.h"
+#include "morph.h"
 #include "mpt.h"
 #include "mpt_internal.h"
 #include "refit.h"
@@ -198,6 +199,17 @@ struct MptContext {
     DBuf<int32_t> skin_joints;
     DBuf<float> skin_weights;
     DBuf<float4> skin_recs;
+    // morph targets (mpt_set_morph, morph.hip): the per-vertex CSR of morph.h.  A morph composes
+    // with a skin and excludes an object table; morph and skin share the rest pose, captured by
+    // whichever is set first and kept until both are gone.  Retained for the call that brings only
+    // the other half: the last accepted weights (morph_w, padded to a multiple of four floats) and
+    // the last accepted palette (skin_recs; skin_posed false: no skin step).  New weights and
+    // records go to the *_stage buffers and are swapped in when the call is accepted.
+    int num_targets = -1;                 // -1: no morph set
+    DBuf<int32_t> morph_row, morph_tgt;
+    DBuf<float> morph_dpos, morph_dnrm, morph_w, morph_w_stage;
+    bool skin_posed = false;
+    DBuf<float4> skin_recs_stage;
     int refit_host_loop = 0;              // test hook (MPT_REFIT_HOST): the refit by the host loop of refit.h
     int light_bvh = 1;                    // MPT_LIGHT_BVH at mpt_create: 0 = one closest-hit traversal per light-hit query
     bool light_bvh_ok = false;            // the light BVH matches the materials (else: the exact closest-hit path)
@@ -1202,13 +1214,26 @@ static int check_scene(const MptScene* s) {
     return MPT_OK;
 }
 
-// The object table of mpt_set_objects or the skin of mpt_set_skin (at most one of them is set), its
-// rest pose and the staging arrays freed.
+// The skin's tables and its retained palette freed (the rest pose stays).
+static void drop_skin_tables(MptContext* c) {
+    c->num_joints = -1;
+    c->skin_posed = false;
+    release_all(c->skin_joints, c->skin_weights, c->skin_recs, c->skin_recs_stage);
+}
+
+// The morph's tables and its retained weights freed (the rest pose stays).
+static void drop_morph_tables(MptContext* c) {
+    c->num_targets = -1;
+    release_all(c->morph_row, c->morph_tgt, c->morph_dpos, c->morph_dnrm, c->morph_w, c->morph_w_stage);
+}
+
+// The object table of mpt_set_objects, or the skin of mpt_set_skin and the morph of mpt_set_morph
+// (a table excludes the other two), the rest pose and the staging arrays freed.
 static void drop_objects(MptContext* c) {
     c->num_objects = -1;
-    c->num_joints = -1;
     release_all(c->vert_obj, c->rest_pos, c->rest_nrm, c->stage_pos, c->stage_nrm, c->xf_recs);
-    release_all(c->skin_joints, c->skin_weights, c->skin_recs);
+    drop_skin_tables(c);
+    drop_morph_tables(c);
 }
 
 // What a scene upload keeps on the host besides its trees: the box pad, the vertices in use, the
@@ -1459,6 +1484,84 @@ bool skin_lds() {
     const char* e = std::getenv("MPT_SKIN_LDS");
     return !(e && e[0] == '0' && e[1] == 0);
 }
+// k_morph takes ONE vertex per lane by default: a lane walks its vertices' entries one after the
+// other, and with four vertices that serial walk costs more than the 16-byte accesses save
+// (339 against 1056 us on the dense 4-target city).  MPT_MORPH_GROUP=4 selects four,
+// MPT_MORPH_LDS=0 the gather through the cache -- tools/morph_time.py measures all four
+int morph_group() {
+    const char* e = std::getenv("MPT_MORPH_GROUP");
+    return e && std::atoi(e) == 4 ? 4 : 1;
+}
+bool morph_lds() {
+    const char* e = std::getenv("MPT_MORPH_LDS");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
+// The pose of a skin and / or a morph evaluated from the shared rest pose: what mpt_update_skin,
+// mpt_update_morph and mpt_update_morph_skin have in common once their arguments are checked.
+// weights (NULL: the retained ones) are the morph's num_targets weights, matrices (NULL: the
+// retained palette, if the skin has been posed) the skin's num_joints matrices.  Everything up to
+// the swap writes scratch only -- the new weights and records included -- so a refusal changes
+// nothing, retained state included.
+int update_pose(MptContext* c, const float* weights, const float* matrices, MptRefitInfo* info, const char* who) {
+    const bool morph = c->num_targets >= 0;
+    const bool skin = matrices || (c->num_joints >= 0 && c->skin_posed);
+    const size_t nv = c->pos.n / 3;
+    if (c->rest_pos.n != c->pos.n || c->rest_nrm.n != c->nrm.n) return fail(MPT_ERR_INVALID_ARGUMENT, "rest pose does not fit the scene");
+    if (skin && (3 * c->skin_joints.n != 4 * c->pos.n || c->skin_weights.n != c->skin_joints.n))
+        return fail(MPT_ERR_INVALID_ARGUMENT, "skin does not fit the scene");
+    if (morph && c->morph_row.n != nv + 1) return fail(MPT_ERR_INVALID_ARGUMENT, "morph does not fit the scene");
+    std::vector<float4> recs;
+    if (matrices) make_skin_records(matrices, c->num_joints, recs);
+    std::vector<float> wpad;
+    if (weights) {
+        wpad.assign(((size_t)c->num_targets + 3) / 4 * 4, 0.0f);
+        std::memcpy(wpad.data(), weights, (size_t)c->num_targets * sizeof(float));
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    float m = 0.0f;
+    bool bad = false;
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = ensure_used_mask(c);
+    if (e == hipSuccess) e = c->stage_pos.alloc(c->pos.n);
+    if (e == hipSuccess) e = c->stage_nrm.alloc(c->nrm.n);
+    if (e == hipSuccess) e = c->xf_red.alloc(2);
+    if (e == hipSuccess && matrices) e = c->skin_recs_stage.upload(recs.data(), recs.size(), st);
+    if (e == hipSuccess && weights) e = c->morph_w_stage.upload(wpad.data(), wpad.size(), st);
+    const float4* d_recs = matrices ? c->skin_recs_stage.p : c->skin_recs.p;
+    const float* d_w = weights ? c->morph_w_stage.p : c->morph_w.p;
+    if (e == hipSuccess && !morph)
+        e = launch_skin(c->rest_pos.p, c->rest_nrm.p, c->skin_joints.p, c->skin_weights.p, c->vert_used.p, (const float*)d_recs,
+                        c->num_joints, (int)nv, c->stage_pos.p, c->stage_nrm.p, c->xf_red.p, skin_group(), skin_lds(), st);
+    if (e == hipSuccess && morph) {
+        MorphLaunch a{};
+        a.rest_pos = c->rest_pos.p; a.rest_nrm = c->rest_nrm.p;
+        a.row = c->morph_row.p; a.tgt = c->morph_tgt.p; a.dpos = c->morph_dpos.p; a.dnrm = c->morph_dnrm.p;
+        a.mweights = d_w; a.num_targets = c->num_targets;
+        if (skin) { a.joints = c->skin_joints.p; a.sweights = c->skin_weights.p; a.recs = (const float*)d_recs; a.num_joints = c->num_joints; }
+        a.used = c->vert_used.p; a.n = (int)nv;
+        a.out_pos = c->stage_pos.p; a.out_nrm = c->stage_nrm.p; a.red = c->xf_red.p;
+        e = launch_morph(a, morph_group(), morph_lds(), st);
+    }
+    if (e == hipSuccess) e = read_reduction(c, &m, &bad);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->has_scene = false;
+        return fail(MPT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
+    if (matrices) {
+        std::swap(c->skin_recs.p, c->skin_recs_stage.p); std::swap(c->skin_recs.n, c->skin_recs_stage.n);
+        c->skin_posed = true;
+    }
+    if (weights) { std::swap(c->morph_w.p, c->morph_w_stage.p); std::swap(c->morph_w.n, c->morph_w_stage.n); }
+    std::swap(c->pos.p, c->stage_pos.p);
+    std::swap(c->nrm.p, c->stage_nrm.p);
+    const float pad = std::ldexp(std::max(m, 1.0f), -20);
+    c->box_pad = pad;
+    return finish_update(c, refit_and_tables(c, pad, nullptr), info, who);
+}
 
 }  // namespace
 
@@ -1492,7 +1595,7 @@ int mpt_set_objects(MptContext* c, const int32_t* vertex_object, int32_t num_ver
     if (!vertex_object) {
         if (num_objects != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
         HIPCHK(hipSetDevice(c->device));
-        if (c->num_joints < 0) drop_objects(c);   // (a skin is mpt_set_skin's to free)
+        if (c->num_joints < 0 && c->num_targets < 0) drop_objects(c);   // (a skin or a morph is its own call's to free)
         return MPT_OK;
     }
     if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
@@ -1570,7 +1673,9 @@ int mpt_set_skin(MptContext* c, const int32_t* joints, const float* weights, int
     if (!joints && !weights) {
         if (num_joints != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
         HIPCHK(hipSetDevice(c->device));
-        if (c->num_objects < 0) drop_objects(c);   // (an object table is mpt_set_objects' to free)
+        // (an object table is mpt_set_objects' to free; with a morph set the rest pose stays)
+        if (c->num_targets >= 0) drop_skin_tables(c);
+        else if (c->num_objects < 0) drop_objects(c);
         return MPT_OK;
     }
     if (!joints || !weights) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1586,21 +1691,26 @@ int mpt_set_skin(MptContext* c, const int32_t* joints, const float* weights, int
     hipError_t e = drain(c);
     if (e == hipSuccess) e = ensure_used_mask(c);
     if (e == hipSuccess) e = dj.upload(joints, 4 * (size_t)num_vertices, st);
+    const bool capture = c->num_targets < 0;   // a morph has captured the rest pose already
     if (e == hipSuccess) e = dw.upload(weights, 4 * (size_t)num_vertices, st);
-    if (e == hipSuccess) e = rp.alloc(c->pos.n);
-    if (e == hipSuccess) e = rn.alloc(c->nrm.n);
-    if (e == hipSuccess) e = hipMemcpyAsync(rp.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(rn.p, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && capture) e = rp.alloc(c->pos.n);
+    if (e == hipSuccess && capture) e = rn.alloc(c->nrm.n);
+    if (e == hipSuccess && capture) e = hipMemcpyAsync(rp.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && capture) e = hipMemcpyAsync(rn.p, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_skin: ") + hipGetErrorString(e));
     }
-    drop_objects(c);
+    if (capture) {
+        drop_objects(c);
+        std::swap(c->rest_pos.p, rp.p); std::swap(c->rest_pos.n, rp.n);
+        std::swap(c->rest_nrm.p, rn.p); std::swap(c->rest_nrm.n, rn.n);
+    } else {
+        drop_skin_tables(c);      // (the new skin is not posed)
+    }
     std::swap(c->skin_joints.p, dj.p); std::swap(c->skin_joints.n, dj.n);
     std::swap(c->skin_weights.p, dw.p); std::swap(c->skin_weights.n, dw.n);
-    std::swap(c->rest_pos.p, rp.p); std::swap(c->rest_pos.n, rp.n);
-    std::swap(c->rest_nrm.p, rn.p); std::swap(c->rest_nrm.n, rn.n);
     c->num_joints = num_joints;
     return MPT_OK;
 }
@@ -1612,38 +1722,93 @@ int mpt_update_skin(MptContext* c, const float* joint_matrices, int32_t num_join
     if (c->num_joints < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no skin set");
     if (num_joints != c->num_joints) return fail(MPT_ERR_INVALID_ARGUMENT, "joint count differs from the table's");
     if (!matrices_finite(joint_matrices, num_joints)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite matrix entry");
-    if (c->rest_pos.n != c->pos.n || c->rest_nrm.n != c->nrm.n || 3 * c->skin_joints.n != 4 * c->pos.n ||
-        c->skin_weights.n != c->skin_joints.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "skin does not fit the scene");
-    std::vector<float4> recs;
-    make_skin_records(joint_matrices, num_joints, recs);
+    return update_pose(c, nullptr, joint_matrices, info, "mpt_update_skin");
+}
+
+int mpt_set_morph(MptContext* c, int32_t num_targets, const int32_t* target_offsets, const int32_t* vertex_ids,
+                  const float* pos_deltas, const float* nrm_deltas, int32_t num_vertices) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!target_offsets && !vertex_ids && !pos_deltas && !nrm_deltas) {
+        if (num_targets != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+        HIPCHK(hipSetDevice(c->device));
+        // (an object table is mpt_set_objects' to free; with a skin set the rest pose stays)
+        if (c->num_joints >= 0) drop_morph_tables(c);
+        else if (c->num_objects < 0) drop_objects(c);
+        return MPT_OK;
+    }
+    if (!target_offsets) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
+    mptmorph::Csr csr;
+    if (const char* bad = mptmorph::to_csr(num_targets, target_offsets, vertex_ids, pos_deltas, nrm_deltas, num_vertices, csr))
+        return fail(MPT_ERR_INVALID_ARGUMENT, bad);
     HIPCHK(hipSetDevice(c->device));
+    // into new buffers, swapped in when all of them are there: a failure leaves what was set
+    const bool capture = c->num_joints < 0;   // a skin has captured the rest pose already
+    const std::vector<float> zeros(((size_t)num_targets + 3) / 4 * 4, 0.0f);
+    const size_t N = csr.tgt.size();
+    DBuf<int32_t> dr, dt;
+    DBuf<float> dp, dn, dw, rp, rn;
     hipStream_t st = c->stream;
-    float m = 0.0f;
-    bool bad = false;
-    // everything up to the swap writes scratch only: a refusal or an error here changes nothing
     hipError_t e = drain(c);
     if (e == hipSuccess) e = ensure_used_mask(c);
-    if (e == hipSuccess) e = c->stage_pos.alloc(c->pos.n);
-    if (e == hipSuccess) e = c->stage_nrm.alloc(c->nrm.n);
-    if (e == hipSuccess) e = c->xf_red.alloc(2);
-    if (e == hipSuccess) e = c->skin_recs.upload(recs.data(), recs.size(), st);
-    if (e == hipSuccess)
-        e = launch_skin(c->rest_pos.p, c->rest_nrm.p, c->skin_joints.p, c->skin_weights.p, c->vert_used.p,
-                        (const float*)c->skin_recs.p, num_joints, (int)(c->pos.n / 3), c->stage_pos.p, c->stage_nrm.p, c->xf_red.p,
-                        skin_group(), skin_lds(), st);
-    if (e == hipSuccess) e = read_reduction(c, &m, &bad);
+    if (e == hipSuccess) e = dr.upload(csr.row.data(), csr.row.size(), st);
+    // (a kernel is never handed a NULL table: a morph without entries keeps one unread entry)
+    if (e == hipSuccess) e = dt.alloc(std::max(N, (size_t)1));
+    if (e == hipSuccess) e = dp.alloc(3 * std::max(N, (size_t)1));
+    if (e == hipSuccess && nrm_deltas) e = dn.alloc(3 * std::max(N, (size_t)1));
+    if (e == hipSuccess && N) e = hipMemcpyAsync(dt.p, csr.tgt.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && N) e = hipMemcpyAsync(dp.p, csr.dpos.data(), 3 * N * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && N && nrm_deltas) e = hipMemcpyAsync(dn.p, csr.dnrm.data(), 3 * N * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = dw.upload(zeros.data(), zeros.size(), st);
+    if (e == hipSuccess && capture) e = rp.alloc(c->pos.n);
+    if (e == hipSuccess && capture) e = rn.alloc(c->nrm.n);
+    if (e == hipSuccess && capture) e = hipMemcpyAsync(rp.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && capture) e = hipMemcpyAsync(rn.p, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        c->has_scene = false;
-        return fail(MPT_ERR_HIP, std::string("mpt_update_skin: ") + hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_morph: ") + hipGetErrorString(e));
     }
-    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
-    std::swap(c->pos.p, c->stage_pos.p);
-    std::swap(c->nrm.p, c->stage_nrm.p);
-    const float pad = std::ldexp(std::max(m, 1.0f), -20);
-    c->box_pad = pad;
-    return finish_update(c, refit_and_tables(c, pad, nullptr), info, "mpt_update_skin");
+    if (capture) {
+        drop_objects(c);          // an object table, or an earlier morph with its rest pose
+        std::swap(c->rest_pos.p, rp.p); std::swap(c->rest_pos.n, rp.n);
+        std::swap(c->rest_nrm.p, rn.p); std::swap(c->rest_nrm.n, rn.n);
+    } else {
+        drop_morph_tables(c);
+    }
+    std::swap(c->morph_row.p, dr.p); std::swap(c->morph_row.n, dr.n);
+    std::swap(c->morph_tgt.p, dt.p); std::swap(c->morph_tgt.n, dt.n);
+    std::swap(c->morph_dpos.p, dp.p); std::swap(c->morph_dpos.n, dp.n);
+    std::swap(c->morph_dnrm.p, dn.p); std::swap(c->morph_dnrm.n, dn.n);
+    std::swap(c->morph_w.p, dw.p); std::swap(c->morph_w.n, dw.n);
+    c->num_targets = num_targets;
+    return MPT_OK;
+}
+
+int mpt_update_morph(MptContext* c, const float* weights, int32_t num_targets, MptRefitInfo* info) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!weights) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (c->num_targets < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no morph set");
+    if (num_targets != c->num_targets) return fail(MPT_ERR_INVALID_ARGUMENT, "target count differs from the tables'");
+    if (!weights_finite(weights, num_targets)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite morph weight");
+    return update_pose(c, weights, nullptr, info, "mpt_update_morph");
+}
+
+int mpt_update_morph_skin(MptContext* c, const float* weights, int32_t num_targets, const float* joint_matrices, int32_t num_joints,
+                          MptRefitInfo* info) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!weights || !joint_matrices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (c->num_targets < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no morph set");
+    if (c->num_joints < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no skin set");
+    if (num_targets != c->num_targets) return fail(MPT_ERR_INVALID_ARGUMENT, "target count differs from the tables'");
+    if (num_joints != c->num_joints) return fail(MPT_ERR_INVALID_ARGUMENT, "joint count differs from the table's");
+    if (!weights_finite(weights, num_targets)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite morph weight");
+    if (!matrices_finite(joint_matrices, num_joints)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite matrix entry");
+    return update_pose(c, weights, joint_matrices, info, "mpt_update_morph_skin");
 }
 
 int mpt_update_vertices_device(MptContext* c, const float* d_vertices, const float* d_normals, int32_t num_vertices,

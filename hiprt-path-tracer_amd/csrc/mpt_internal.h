@@ -442,6 +442,33 @@ bool skin_host(const float* rest_pos, const float* rest_nrm, const int32_t* join
                const float* recs, float* out_pos, float* out_nrm);
 const char* check_skin_table(const int32_t* joints, const float* weights, size_t num_vertices, int32_t num_joints);
 void make_skin_records(const float* matrices, int32_t num_joints, std::vector<float4>& recs);
+// morph.hip (morph.h): n rest-pose vertices morphed by the per-vertex CSR (row: n + 1 offsets; tgt,
+// dpos and dnrm -- NULL: no normal deltas -- per entry) with num_targets weights (mweights, padded
+// with zeros to a multiple of four floats, 16-byte aligned) and then, when recs is not NULL, skinned
+// as by launch_skin, into out_pos / out_nrm; red, group and lds as launch_skin (lds stages the
+// weights up to MPT_MORPH_LDS_TARGETS and, fused, the palette up to MPT_SKIN_LDS_JOINTS: both or
+// neither).
+struct MorphLaunch {
+    const float* rest_pos;
+    const float* rest_nrm;
+    const int32_t* row;
+    const int32_t* tgt;
+    const float* dpos;
+    const float* dnrm;
+    const float* mweights;
+    int num_targets;
+    const int32_t* joints;    // the skin: NULL recs = no skin step
+    const float* sweights;
+    const float* recs;
+    int num_joints;
+    const uint8_t* used;
+    int n;
+    float* out_pos;
+    float* out_nrm;
+    uint32_t* red;
+};
+hipError_t launch_morph(const MorphLaunch& a, int group, bool lds, hipStream_t st);
+bool weights_finite(const float* w, int32_t n);
 // the scene BVH as mpt_upload_scene builds it (rebuilt shallower while too deep for stack_limit
 // entries); returns the stack limit in force (MPT_BVH_MAX_STACK)
 int build_scene_bvh8(const float* vertices, const int32_t* indices, int32_t num_triangles, BVH8& out, int stack_limit);

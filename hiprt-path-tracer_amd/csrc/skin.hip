@@ -41,20 +41,6 @@ using mptxform::abs_max3;
 using mptxform::finite3;
 using namespace vertio;
 
-// The 4 indices and 4 weights of vertex v: 16-byte loads when the arrays are aligned (G = 4).
-template <int G>
-__device__ inline void load_influences(const int32_t* __restrict__ joints, const float* __restrict__ weights, size_t v, int32_t* j,
-                                       float* w) {
-    if constexpr (G == 4) {
-        const int4 a = *(const int4*)(joints + 4 * v);
-        const float4 b = *(const float4*)(weights + 4 * v);
-        j[0] = a.x; j[1] = a.y; j[2] = a.z; j[3] = a.w;
-        w[0] = b.x; w[1] = b.y; w[2] = b.z; w[3] = b.w;
-    } else {
-        for (int s = 0; s < 4; s++) { j[s] = joints[4 * v + s]; w[s] = weights[4 * v + s]; }
-    }
-}
-
 template <int G, bool LDS>
 __global__ void __launch_bounds__(256) k_skin(const float* __restrict__ rest_pos, const float* __restrict__ rest_nrm,
                                               const int32_t* __restrict__ joints, const float* __restrict__ weights,

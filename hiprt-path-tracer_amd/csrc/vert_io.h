@@ -1,6 +1,7 @@
-// vert_io.h -- what the kernels over vertex arrays share (xform.hip, skin.hip): a lane's group of G
-// vertices loaded and stored with 16-byte accesses, the used-vertex mask, and the block reduction of
-// the largest |coordinate| and the non-finite flag.  Device code: included by .hip files only.
+// vert_io.h -- what the kernels over vertex arrays share (xform.hip, skin.hip, morph.hip): a lane's
+// group of G vertices loaded and stored with 16-byte accesses, the used-vertex mask, a vertex's skin
+// influences, a group's CSR row offsets, and the block reduction of the largest |coordinate| and
+// the non-finite flag.  Device code: included by .hip files only.
 #ifndef MPT_VERT_IO_H
 #define MPT_VERT_IO_H
 
@@ -60,6 +61,34 @@ __device__ static inline void load_mask(const uint8_t* __restrict__ used, size_t
         for (int k = 0; k < 4; k++) u[k] = ((w >> (8 * k)) & 0xffu) != 0;
     } else {
         for (int k = 0; k < G; k++) u[k] = k < cnt && used[v0 + k] != 0;
+    }
+}
+
+// The 4 joint indices and 4 weights of vertex v (skin.hip, morph.hip): 16-byte loads when the
+// arrays are aligned (G = 4).
+template <int G>
+__device__ static inline void load_influences(const int32_t* __restrict__ joints, const float* __restrict__ weights, size_t v, int32_t* j,
+                                              float* w) {
+    if constexpr (G == 4) {
+        const int4 a = *(const int4*)(joints + 4 * v);
+        const float4 b = *(const float4*)(weights + 4 * v);
+        j[0] = a.x; j[1] = a.y; j[2] = a.z; j[3] = a.w;
+        w[0] = b.x; w[1] = b.y; w[2] = b.z; w[3] = b.w;
+    } else {
+        for (int s = 0; s < 4; s++) { j[s] = joints[4 * v + s]; w[s] = weights[4 * v + s]; }
+    }
+}
+
+// The G + 1 CSR row offsets row[v0 .. v0 + cnt] of a lane's group (morph.hip): one 16-byte load and
+// a dword for a whole group of 4; the offsets past cnt repeat the last one (empty rows).
+template <int G>
+__device__ static inline void load_rows(const int32_t* __restrict__ row, size_t v0, int cnt, int32_t* r) {
+    if (G == 4 && cnt == 4) {
+        const int4 a = *(const int4*)(row + v0);
+        r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
+        r[4] = row[v0 + 4];
+    } else {
+        for (int k = 0; k <= G; k++) r[k] = row[v0 + (size_t)(k < cnt ? k : cnt)];
     }
 }
 

@@ -48,9 +48,9 @@ XFORM_FN void xform_pos(const float* m, const float* p, float* o) {
     for (int r = 0; r < 3; r++) o[r] = ((m[4 * r] * p[0] + m[4 * r + 1] * p[1]) + m[4 * r + 2] * p[2]) + m[4 * r + 3];
 }
 
-XFORM_FN void xform_nrm(const float* N, const float* n, float* o) {
-    float t[3];
-    for (int r = 0; r < 3; r++) t[r] = (N[3 * r] * n[0] + N[3 * r + 1] * n[1]) + N[3 * r + 2] * n[2];
+// The tail of every normal: t normalised when its squared length is positive and finite, else the
+// rest normal n unchanged (morph.h shares it).
+XFORM_FN void nrm_tail(const float* t, const float* n, float* o) {
     const float l2 = (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2];
     if (l2 > 0.0f && l2 <= F_MAX) {
         const float l = sqrtf(l2);
@@ -58,6 +58,12 @@ XFORM_FN void xform_nrm(const float* N, const float* n, float* o) {
     } else {
         for (int r = 0; r < 3; r++) o[r] = n[r];
     }
+}
+
+XFORM_FN void xform_nrm(const float* N, const float* n, float* o) {
+    float t[3];
+    for (int r = 0; r < 3; r++) t[r] = (N[3 * r] * n[0] + N[3 * r + 1] * n[1]) + N[3 * r + 2] * n[2];
+    nrm_tail(t, n, o);
 }
 
 // One vertex of an object (rec: its 21 floats).  pass: the vertex passes through -- object -1, or

@@ -167,6 +167,23 @@ void GPURenderer::update_skin(const float* joint_matrices, int32_t num_joints, M
     reset();   // as update_vertices: what was accumulated shows the old geometry
 }
 
+void GPURenderer::set_morph(int32_t num_targets, const int32_t* target_offsets, const int32_t* vertex_ids, const float* pos_deltas,
+                            const float* nrm_deltas, int32_t num_vertices) {
+    for (MptContext* c : m_ctxs) check(mpt_set_morph(c, num_targets, target_offsets, vertex_ids, pos_deltas, nrm_deltas, num_vertices));
+}
+
+void GPURenderer::update_morph(const float* weights, int32_t num_targets, MptRefitInfo* info) {
+    for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_update_morph(m_ctxs[k], weights, num_targets, k == 0 ? info : nullptr));
+    reset();   // as update_vertices: what was accumulated shows the old geometry
+}
+
+void GPURenderer::update_morph_skin(const float* weights, int32_t num_targets, const float* joint_matrices, int32_t num_joints,
+                                    MptRefitInfo* info) {
+    for (size_t k = 0; k < m_ctxs.size(); k++)
+        check(mpt_update_morph_skin(m_ctxs[k], weights, num_targets, joint_matrices, num_joints, k == 0 ? info : nullptr));
+    reset();
+}
+
 void GPURenderer::rebuild_bvh(MptRebuildInfo* info, int32_t mode) {
     for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_rebuild_bvh_mode(m_ctxs[k], mode, k == 0 ? info : nullptr));
     // (no reset: results do not depend on the tree)

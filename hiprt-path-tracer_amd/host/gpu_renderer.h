@@ -149,6 +149,19 @@ public:
     // restarts as after update_vertices.  info (optional): the first context's report.
     void set_skin(const int32_t* joints, const float* weights, int32_t num_vertices, int32_t num_joints);
     void update_skin(const float* joint_matrices, int32_t num_joints, MptRefitInfo* info = nullptr);
+    // set_morph / update_morph / update_morph_skin (no counterpart in the reference): morph targets
+    // of the flat scene, applied before the skin.  set_morph gives every context the tables, sparse
+    // by target (mpt_set_morph; NULL tables with 0 targets remove the morph); a morph composes with
+    // the skin of set_skin -- they share the rest pose, captured by whichever is set first -- and
+    // excludes the objects of set_objects.  update_morph evaluates one weight per target with the
+    // skin's last pose, update_morph_skin sets weights and joint matrices in one call: one kernel
+    // and one refit on every context's GPU.  The accumulation restarts as after update_vertices.
+    // info (optional): the first context's report.
+    void set_morph(int32_t num_targets, const int32_t* target_offsets, const int32_t* vertex_ids, const float* pos_deltas,
+                   const float* nrm_deltas_or_null, int32_t num_vertices);
+    void update_morph(const float* weights, int32_t num_targets, MptRefitInfo* info = nullptr);
+    void update_morph_skin(const float* weights, int32_t num_targets, const float* joint_matrices, int32_t num_joints,
+                           MptRefitInfo* info = nullptr);
     // rebuild_bvh (no counterpart in the reference): every context rebuilds its BVHs on its GPU
     // from the positions it holds (mpt_rebuild_bvh_mode), e.g. once update_vertices reports a large
     // area_ratio.  The accumulation continues: traversal results do not depend on the tree.

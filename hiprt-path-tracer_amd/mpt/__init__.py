@@ -23,7 +23,7 @@ from ._build import LIB_PATH
 
 __all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
            "display_host", "write_png", "denoise_host", "bvh_refit_host", "bvh_build_host", "transform_host", "skin_host",
-           "SKIN_LDS_JOINTS"]
+           "SKIN_LDS_JOINTS", "morph_host", "MORPH_LDS_TARGETS"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -40,9 +40,11 @@ SYMBOLS = [
     "mpt_rebuild_bvh_mode", "mpt_bvh_build_host_mode", "mpt_upload_scene_mode",
     "mpt_set_objects", "mpt_update_transforms", "mpt_update_vertices_device", "mpt_transform_host",
     "mpt_set_skin", "mpt_update_skin", "mpt_skin_host",
+    "mpt_set_morph", "mpt_update_morph", "mpt_update_morph_skin", "mpt_morph_host",
 ]
 
 SKIN_LDS_JOINTS = abi.SKIN_LDS_JOINTS
+MORPH_LDS_TARGETS = abi.MORPH_LDS_TARGETS
 
 
 class MptError(RuntimeError):
@@ -136,6 +138,10 @@ def lib() -> C.CDLL:
     L.mpt_set_skin.argtypes = [vp, vp, vp, i32, i32]
     L.mpt_update_skin.argtypes = [vp, vp, i32, C.POINTER(abi.RefitInfo)]
     L.mpt_skin_host.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp]
+    L.mpt_set_morph.argtypes = [vp, i32, vp, vp, vp, vp, i32]
+    L.mpt_update_morph.argtypes = [vp, vp, i32, C.POINTER(abi.RefitInfo)]
+    L.mpt_update_morph_skin.argtypes = [vp, vp, i32, vp, i32, C.POINTER(abi.RefitInfo)]
+    L.mpt_morph_host.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -391,6 +397,69 @@ def skin_host(rest_vertices, rest_normals, joints, weights, matrices):
     return ov, on
 
 
+def _morph_tables(morph, who):
+    """A scene.MorphData, or a list with one (vertex ids, position deltas [n, 3], normal deltas
+    [n, 3] or None) per target -> (T, offsets int32 [T + 1], ids int32 [N], position deltas float32
+    [N, 3], normal deltas float32 [N, 3] or None: no target has any).  Each target's ids are sorted
+    for the caller (a stable sort, the deltas follow); a vertex twice in one target raises
+    ValueError here, before any library call."""
+    if isinstance(morph, scene.MorphData):
+        targets = [(morph.vertex_ids[a:b], morph.pos_deltas[a:b], None if morph.nrm_deltas is None else morph.nrm_deltas[a:b])
+                   for a, b in zip(morph.target_offsets[:-1], morph.target_offsets[1:])]
+    else:
+        targets = list(morph)
+    any_n = any(len(t) > 2 and t[2] is not None for t in targets)
+    off, ids, dps, dns = [0], [], [], []
+    for k, t in enumerate(targets):
+        i = np.asarray(t[0], np.int64).reshape(-1)
+        dp = np.asarray(t[1], np.float32).reshape(-1, 3)
+        dn = None if len(t) < 3 or t[2] is None else np.asarray(t[2], np.float32).reshape(-1, 3)
+        if len(dp) != len(i) or (dn is not None and len(dn) != len(i)):
+            raise ValueError(f"{who}: target {k}: {len(i)} ids for {len(dp)} position deltas"
+                             + ("" if dn is None else f" and {len(dn)} normal deltas"))
+        if len(i) and (i.min() < -2**31 or i.max() >= 2**31):
+            raise ValueError(f"{who}: target {k}: a vertex id outside int32")
+        o = np.argsort(i, kind="stable")
+        i = i[o]
+        if np.any(i[1:] == i[:-1]):
+            raise ValueError(f"{who}: target {k}: a vertex appears more than once")
+        ids.append(i.astype(np.int32))
+        dps.append(dp[o])
+        if any_n:
+            dns.append(np.zeros_like(dp) if dn is None else dn[o])
+        off.append(off[-1] + len(i))
+    cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(shape, dt), dt)
+    return (len(targets), np.asarray(off, np.int32), cat(ids, (0,), np.int32), cat(dps, (0, 3), np.float32),
+            cat(dns, (0, 3), np.float32) if any_n else None)
+
+
+def _morph_weights(weights, who):
+    w = np.ascontiguousarray(weights, np.float32)
+    if w.ndim != 1:
+        raise ValueError(f"{who}: weights of shape {w.shape}, not [T]")
+    return w
+
+
+def morph_host(rest_vertices, rest_normals, morph, weights):
+    """mpt_morph_host, no GPU: the host loop of csrc/morph.h -- the positions ([V, 3] float32) and,
+    when rest_normals is given, the vertex normals that GPURenderer.update_morph(weights) leaves on
+    the device for this rest pose and morph (a scene.MorphData or a list of (ids, position deltas,
+    normal deltas or None) per target, as set_morph takes; weights: float32 [T]) when no skin is
+    posed.  Returns (vertices, normals or None)."""
+    v = np.ascontiguousarray(rest_vertices, np.float32).reshape(-1, 3)
+    n = None if rest_normals is None else np.ascontiguousarray(rest_normals, np.float32).reshape(-1, 3)
+    if n is not None and n.shape != v.shape:
+        raise ValueError(f"morph_host: {n.shape[0]} normals for {v.shape[0]} vertices")
+    T, off, ids, dp, dn = _morph_tables(morph, "morph_host")
+    w = _morph_weights(weights, "morph_host")
+    if len(w) != T:
+        raise ValueError(f"morph_host: {len(w)} weights for {T} targets")
+    ov = np.empty_like(v)
+    on = None if n is None else np.empty_like(n)
+    _check(lib().mpt_morph_host(_p(v), _p(n), len(v), T, _p(off), _p(ids), _p(dp), _p(dn), _p(w), _p(ov), _p(on)))
+    return ov, on
+
+
 def _on_device(a):
     """A torch tensor in GPU memory (anything else, a CPU tensor included, is a host array)."""
     return bool(getattr(a, "is_cuda", False))
@@ -407,6 +476,7 @@ class GPURenderer:
         self.device = device
         self.frame = None
         self._n_mats = 0
+        self._n_verts = 0
 
     # --- scene / resources -----------------------------------------------------
     def set_scene(self, sd: "scene.SceneData", build=None, info=False):
@@ -425,6 +495,7 @@ class GPURenderer:
             ri = abi.RebuildInfo() if info else None
             _check(lib().mpt_upload_scene_mode(self.h, C.byref(s), int(build), C.byref(ri) if info else None))
         self._n_mats = len(sd.materials)
+        self._n_verts = len(np.asarray(sd.vertices).reshape(-1, 3))
         return ri
 
     def update_materials(self, materials):
@@ -516,6 +587,39 @@ class GPURenderer:
         m = _matrices(matrices, "update_skin")
         ri = abi.RefitInfo() if info else None
         _check(lib().mpt_update_skin(self.h, _p(m), len(m), C.byref(ri) if info else None))
+        return ri
+
+    def set_morph(self, morph):
+        """mpt_set_morph: morph is a scene.MorphData (SceneData.morph) or a list with one (vertex
+        ids, position deltas [n, 3], normal deltas [n, 3] or None) per target; each target's ids are
+        sorted here and a vertex twice in one target raises ValueError.  Pose = skin(morph(rest
+        pose)): a morph composes with the skin of set_skin -- they share the rest pose, captured by
+        whichever is set first -- and excludes the objects of set_objects.  The weights start at
+        zero.  morph=None removes the morph."""
+        if morph is None:
+            _check(lib().mpt_set_morph(self.h, 0, None, None, None, None, 0))
+            return
+        T, off, ids, dp, dn = _morph_tables(morph, "set_morph")
+        # (the tables do not say how many vertices the scene has: set_scene's count)
+        _check(lib().mpt_set_morph(self.h, T, _p(off), _p(ids), _p(dp), _p(dn), self._n_verts))
+
+    def update_morph(self, weights, info=False):
+        """mpt_update_morph: one weight per target ([T] float32) applied to the rest pose on the
+        GPU, followed in the same kernel by the skin's last pose when update_skin has set one, then
+        the refit of both BVHs: 4 bytes per target cross the bus, no vertex array.  The next frame
+        must carry need_to_reset.  info=True returns the abi.RefitInfo, else None."""
+        w = _morph_weights(weights, "update_morph")
+        ri = abi.RefitInfo() if info else None
+        _check(lib().mpt_update_morph(self.h, _p(w), len(w), C.byref(ri) if info else None))
+        return ri
+
+    def update_morph_skin(self, weights, matrices, info=False):
+        """mpt_update_morph_skin: update_morph(weights) and update_skin(matrices) as one call: one
+        kernel, one refit."""
+        w = _morph_weights(weights, "update_morph_skin")
+        m = _matrices(matrices, "update_morph_skin")
+        ri = abi.RefitInfo() if info else None
+        _check(lib().mpt_update_morph_skin(self.h, _p(w), len(w), _p(m), len(m), C.byref(ri) if info else None))
         return ri
 
     def rebuild_bvh(self, info=False, mode=abi.BUILD_LBVH):

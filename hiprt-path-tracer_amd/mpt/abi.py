@@ -462,6 +462,7 @@ class RefitInfo(C.Structure):
 
 BUILD_LBVH, BUILD_PLOC, BUILD_SAH = 0, 1, 3   # MPT_BUILD_*: the build modes of mpt_rebuild_bvh_mode (2 is none)
 SKIN_LDS_JOINTS = 256   # MPT_SKIN_LDS_JOINTS: the largest palette mpt_update_skin's kernel stages in LDS
+MORPH_LDS_TARGETS = 4096   # MPT_MORPH_LDS_TARGETS: the most morph weights the morph kernel stages in LDS
 
 
 class RebuildInfo(C.Structure):

@@ -72,6 +72,35 @@ class SkinData:
         return len(self.joint_nodes)
 
 
+class MorphData:
+    """The morph targets of a glTF file's mesh nodes over SceneData's flat vertices: what
+    GPURenderer.set_morph and mpt.morph_host take.  Like the skin's palette, each mesh node with
+    targets gets its own stretch of the target list (a mesh instanced by two nodes has two).
+
+    The deltas are in WORLD space, as SceneData.vertices are: position deltas times the node's linear
+    part R, normal deltas times its inverse transpose and divided by the same |RIT n| the rest
+    normal was divided by, so that n + sum w*dn is parallel to the transformed local sum.  glTF
+    morphs in the mesh's own space and then skins; with SkinData.bind = inverse_bind @ inverse(M)
+    the skin first takes a world-space vertex back to mesh space, so the world-space morph followed
+    by the skin is glTF's mesh-space morph followed by the skin (M is affine: M (p + d) = M p + R d).
+    Entries whose position and normal deltas are both exactly zero are dropped, so a sparse accessor
+    stays sparse.  A primitive without NORMAL, or a target without NORMAL deltas, has zero normal
+    deltas; nrm_deltas is None when no target of the file has any.  TANGENT deltas are ignored."""
+
+    def __init__(self):
+        self.target_offsets = None   # int32 [T + 1]: target t owns the entries [offsets[t], offsets[t + 1])
+        self.vertex_ids = None       # int32 [N], ascending inside a target
+        self.pos_deltas = None       # float32 [N, 3]
+        self.nrm_deltas = None       # float32 [N, 3] or None
+        self.target_node = None      # int32 [T]: the mesh node of every target
+        self.target_index = None     # int32 [T]: its index among that node's mesh's targets
+        self.default_weights = None  # float32 [T]: node.weights, else mesh.weights, else 0
+
+    @property
+    def num_targets(self):
+        return len(self.target_node)
+
+
 def skin_matrices(sd, node_locals=None):
     """The joint matrices of a pose for GPURenderer.update_skin / mpt.skin_host: float32 [J, 3, 4],
     global_j @ sd.skin.bind[j], the global joint transforms recomputed in float64 from the file's
@@ -111,6 +140,7 @@ class SceneData:
         self.camera_info = None       # dict for make_camera
         self.vertex_object = None     # int32 [V] or None: per vertex the ordinal of its mesh node (glTF loader)
         self.skin = None              # SkinData or None: the file's skinned mesh nodes (glTF loader)
+        self.morph = None             # MorphData or None: the file's morph targets (glTF loader)
         self.name = ""
 
     @property
@@ -434,6 +464,7 @@ def load_gltf(path, aspect_override=None):
     need_default = False
     n_mesh_nodes = 0
     pal_nodes, pal_bind = [], []     # SceneData.skin: the palette, one stretch per skinned mesh node
+    tgt_node, tgt_index, tgt_weight = [], [], []   # SceneData.morph: the targets
     for ni, n in enumerate(g["nodes"]):
         if "mesh" not in n or ni not in world:
             continue
@@ -454,7 +485,16 @@ def load_gltf(path, aspect_override=None):
             for k, jn in enumerate(sk["joints"]):
                 pal_nodes.append(jn)
                 pal_bind.append(ibm[k] @ Minv)
-        for prim in g["meshes"][n["mesh"]]["primitives"]:
+        mesh = g["meshes"][n["mesh"]]
+        n_tgt = max([len(pr.get("targets", [])) for pr in mesh["primitives"]], default=0)
+        tgt0 = len(tgt_node)             # SceneData.morph: one stretch of targets per mesh node with targets
+        if n_tgt:
+            dw = n.get("weights", mesh.get("weights", [0.0] * n_tgt))
+            for k in range(n_tgt):
+                tgt_node.append(ni)
+                tgt_index.append(k)
+                tgt_weight.append(float(dw[k]) if k < len(dw) else 0.0)
+        for prim in mesh["primitives"]:
             mode = prim.get("mode", 4)
             if mode not in (4, 5, 6):
                 # points / lines have no surface: ASSIMP hands them over as 1- or 2-index faces,
@@ -467,7 +507,8 @@ def load_gltf(path, aspect_override=None):
             nrm = None
             if "NORMAL" in att:
                 nrm = _accessor(g, bins, att["NORMAL"]).astype(np.float64) @ RIT.T
-                nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-30)
+                nlen = np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-30)
+                nrm /= nlen
                 nrm = nrm.astype(np.float32)
             uv = _accessor(g, bins, att["TEXCOORD_0"]).astype(np.float32) if "TEXCOORD_0" in att else None
             if "indices" in prim:
@@ -490,7 +531,16 @@ def load_gltf(path, aspect_override=None):
                 if jnt.min() < 0 or jnt.max() >= len(pal_nodes) - pal0:
                     raise ValueError(f"{os.path.basename(path)}: mesh {n['mesh']}: joint index outside its skin")
                 infl = ((jnt + pal0).astype(np.int32), wgt.astype(np.float32))
-            inst.append((mi, pos, nrm, uv, _triangles(mode, idx), node_ord, infl))
+            deltas = []                  # per target of the primitive: world-space (dpos, dnrm or None)
+            for tg in prim.get("targets", []):
+                dp = np.zeros((len(pos), 3), np.float32)
+                if "POSITION" in tg:
+                    dp = (_accessor(g, bins, tg["POSITION"]).astype(np.float64) @ R.T).astype(np.float32)
+                dn = None
+                if "NORMAL" in tg and nrm is not None:
+                    dn = ((_accessor(g, bins, tg["NORMAL"]).astype(np.float64) @ RIT.T) / nlen).astype(np.float32)
+                deltas.append((dp, dn))
+            inst.append((mi, pos, nrm, uv, _triangles(mode, idx), node_ord, infl, (tgt0, deltas)))
 
     total_mats = n_mat + (1 if need_default else 0)
     tex_idx, const_em, textures, tex_count = _load_textures(g, bins, base, materials_json)
@@ -506,9 +556,11 @@ def load_gltf(path, aspect_override=None):
     sd.name = os.path.splitext(os.path.basename(path))[0]
     tri, verts, nrms, hasn, uvs, mids, vobj, vjnt, vwgt = [], [], [], [], [], [], [], [], []
     voff = 0
+    m_ids, m_dp, m_dn = ([[] for _ in tgt_node] for _ in range(3))
+    m_has_n = [False]
     # PreTransformVertices: output meshes ordered by material index
     for mi in range(total_mats):
-        for (m, pos, nrm, uv, idx, node_ord, infl) in inst:
+        for (m, pos, nrm, uv, idx, node_ord, infl, (tgt0, deltas)) in inst:
             if m != mi:
                 continue
             tri.append(idx + voff)
@@ -525,6 +577,13 @@ def load_gltf(path, aspect_override=None):
             vobj.append(np.full(len(pos), node_ord, np.int32))
             vjnt.append(infl[0] if infl else np.zeros((len(pos), 4), np.int32))
             vwgt.append(infl[1] if infl else np.zeros((len(pos), 4), np.float32))
+            for k, (dp, dn) in enumerate(deltas):    # (voff grows: a target's ids come out ascending)
+                keep = np.any(dp != 0, axis=1) if dn is None else np.any(dp != 0, axis=1) | np.any(dn != 0, axis=1)
+                rows = np.nonzero(keep)[0]
+                m_ids[tgt0 + k].append(rows + voff)
+                m_dp[tgt0 + k].append(dp[rows])
+                m_dn[tgt0 + k].append(np.zeros((len(rows), 3), np.float32) if dn is None else dn[rows])
+                m_has_n[0] |= dn is not None
             voff += len(pos)
     sd.triangle_indices = np.concatenate(tri).astype(np.int32).ravel()
     sd.vertices = np.concatenate(verts).astype(np.float32)
@@ -545,6 +604,17 @@ def load_gltf(path, aspect_override=None):
                 sk.node_parents[c] = ni
         sk.node_locals = np.stack([_node_matrix(nd) for nd in g["nodes"]])
         sd.skin = sk
+    if tgt_node:
+        md = MorphData()
+        cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(shape, dt), dt)
+        md.target_offsets = np.concatenate([[0], np.cumsum([sum(len(a) for a in t) for t in m_ids])]).astype(np.int32)
+        md.vertex_ids = cat([a for t in m_ids for a in t], (0,), np.int32)
+        md.pos_deltas = cat([a for t in m_dp for a in t], (0, 3), np.float32)
+        md.nrm_deltas = cat([a for t in m_dn for a in t], (0, 3), np.float32) if m_has_n[0] else None
+        md.target_node = np.array(tgt_node, np.int32)
+        md.target_index = np.array(tgt_index, np.int32)
+        md.default_weights = np.array(tgt_weight, np.float32)
+        sd.morph = md
     sd.materials = mats
     sd.textures = textures
 

@@ -742,6 +742,21 @@ def write_skinned_gltf(path: str, rings: int = 7, sides: int = 8, joints: int = 
     * nodes 1 .. joints: the chain, the root placed by a matrix, each child one segment up its
       parent's y axis.
     * then an unskinned floor quad with an emissive strip (a second mesh, two materials) and a camera."""
+    return _write_tube_gltf(path, rings, sides, joints, length, radius, normalized_weights)
+
+
+def write_morphed_gltf(path: str, skinned: bool = True, rings: int = 7, sides: int = 8) -> str:
+    """write_skinned_gltf's scene with two morph targets on the tube (mesh.weights [0.25, 0.5]):
+    target 0 bulges every ring outwards and has NORMAL deltas; target 1 is a sparse accessor that
+    moves the middle ring only and has no NORMAL.  The floor has no targets.  skinned=False leaves
+    the skin out: the tube's node then places it by its own rotation and translation, so the
+    deltas' way into world space is exercised either way."""
+    return _write_tube_gltf(path, rings, sides, 3, 1.8, 0.25, True, morph=True, skinned=skinned)
+
+
+def _write_tube_gltf(path, rings, sides, joints, length, radius, normalized_weights, morph=False, skinned=True):
+    """The scene of write_skinned_gltf; morph: with write_morphed_gltf's two targets; skinned=False:
+    without the skin (the joint nodes stay in the file, unused)."""
     import base64
     import json
 
@@ -800,9 +815,11 @@ def write_skinned_gltf(path: str, rings: int = 7, sides: int = 8, joints: int = 
         accessors.append(a)
         return len(accessors) - 1
 
-    tube = {"attributes": {"POSITION": acc(P, 5126, "VEC3"), "NORMAL": acc(N, 5126, "VEC3"), "JOINTS_0": acc(J, 5121, "VEC4"),
-                           "WEIGHTS_0": acc(Wt, 5123 if normalized_weights else 5126, "VEC4", normalized_weights)},
-            "indices": acc(I, 5123, "SCALAR"), "material": 0}
+    tube = {"attributes": {"POSITION": acc(P, 5126, "VEC3"), "NORMAL": acc(N, 5126, "VEC3")}}
+    if skinned:
+        tube["attributes"]["JOINTS_0"] = acc(J, 5121, "VEC4")
+        tube["attributes"]["WEIGHTS_0"] = acc(Wt, 5123 if normalized_weights else 5126, "VEC4", normalized_weights)
+    tube.update({"indices": acc(I, 5123, "SCALAR"), "material": 0})
     fl_p, fl_n = acc(FP, 5126, "VEC3"), acc(FN, 5126, "VEC3")
     floor = [{"attributes": {"POSITION": fl_p, "NORMAL": fl_n}, "indices": acc(np.array([0, 1, 2, 0, 2, 3], np.uint16), 5123, "SCALAR"),
               "material": 1},
@@ -811,6 +828,23 @@ def write_skinned_gltf(path: str, rings: int = 7, sides: int = 8, joints: int = 
     # the transposed ibm, flattened row by row, is glTF's column-major MAT4
     skin = {"joints": list(range(1, joints + 1)),
             "inverseBindMatrices": acc(ibm.transpose(0, 2, 1).reshape(-1, 16), 5126, "MAT4")}
+    tube_mesh = {"primitives": [tube]}
+    if morph:
+        h = np.repeat(ys, sides)[:, None] / length
+        out = np.tile(ring, (rings, 1))
+        bulge = (out * (0.05 + 0.1 * np.sin(np.pi * h))).astype(np.float32)
+        tilt = (np.array([[0.0, 0.3, 0.0]]) * np.cos(np.pi * h)).astype(np.float32)
+        mid = np.arange(sides, dtype=np.uint16) + np.uint16((rings // 2) * sides)
+        push = (ring * 0.15 + [0.0, 0.05, 0.0]).astype(np.float32)
+        sp_i, sp_v = acc(mid, 5123, "SCALAR"), acc(push, 5126, "VEC3")
+        sparse = {"componentType": 5126, "count": len(P), "type": "VEC3", "min": np.minimum(push.min(0), 0.0).tolist(),
+                  "max": np.maximum(push.max(0), 0.0).tolist(),
+                  "sparse": {"count": sides, "indices": {"bufferView": accessors[sp_i]["bufferView"], "componentType": 5123},
+                             "values": {"bufferView": accessors[sp_v]["bufferView"]}}}
+        accessors.append(sparse)
+        sp = len(accessors) - 1
+        tube["targets"] = [{"POSITION": acc(bulge, 5126, "VEC3"), "NORMAL": acc(tilt, 5126, "VEC3")}, {"POSITION": sp}]
+        tube_mesh["weights"] = [0.25, 0.5]
     nodes = [{"mesh": 0, "skin": 0, "rotation": [0.0, 0.0, math.sin(math.radians(12.5)), math.cos(math.radians(12.5))],
               "translation": [-0.4, 0.1, -0.2]},
              {"matrix": W.T.reshape(-1).tolist(), "children": [2]}]
@@ -829,11 +863,13 @@ def write_skinned_gltf(path: str, rings: int = 7, sides: int = 8, joints: int = 
     ]
     binary = b"".join(chunks)
     g = {"asset": {"version": "2.0"}, "scene": 0, "scenes": [{"nodes": [0, 1, joints + 1, joints + 2]}], "nodes": nodes,
-         "meshes": [{"primitives": [tube]}, {"primitives": floor}], "skins": [skin], "materials": materials,
+         "meshes": [tube_mesh, {"primitives": floor}], "skins": [skin], "materials": materials,
          "accessors": accessors, "bufferViews": views,
          "buffers": [{"byteLength": len(binary), "uri": "data:application/octet-stream;base64," + base64.b64encode(binary).decode()}],
          "cameras": [{"type": "perspective", "perspective": {"yfov": 0.75, "aspectRatio": 1.0, "znear": 0.05, "zfar": 50.0}}],
          "extensionsUsed": ["KHR_materials_emissive_strength"]}
+    if not skinned:
+        del g["skins"], nodes[0]["skin"]
     with open(path, "w") as f:
         json.dump(g, f)
     return path

@@ -604,7 +604,8 @@ int mpt_update_vertices(MptContext* ctx, const float* vertices, const float* ver
  * mpt_update_vertices, mpt_update_vertices_device and rebuilds leave the rest pose as captured;
  * mpt_upload_scene and mpt_upload_scene_mode drop the objects (a new scene).  NULL with
  * num_objects 0 frees the table, the rest pose and the staging arrays.  A skin (mpt_set_skin)
- * and an object table exclude each other: setting the table drops a skin.
+ * and an object table exclude each other: setting the table drops a skin, and a morph
+ * (mpt_set_morph) with it.
  * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, for a vertex count
  * other than the scene's, num_objects < 1 with a table, or an id out of range. */
 int mpt_set_objects(MptContext* ctx, const int32_t* vertex_object, int32_t num_vertices, int32_t num_objects);
@@ -662,6 +663,8 @@ int mpt_transform_host(const float* rest_vertices, const float* rest_normals_or_
  * mpt_upload_scene_mode drop either.  mpt_update_vertices, mpt_update_vertices_device and rebuilds
  * leave the rest pose as captured.  NULL tables with num_joints 0 free the skin, the rest pose and
  * the staging arrays (and leave an object table alone, as mpt_set_objects(NULL) leaves a skin).
+ * A morph (mpt_set_morph, below) composes with the skin and shares its rest pose: with a morph set,
+ * mpt_set_skin does not capture the rest pose again, and NULL tables free only the skin's tables.
  * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, for a vertex count
  * other than the scene's, num_joints < 1 with a table, an index outside [0, num_joints) in any slot
  * (whatever its weight) or a weight that is not finite. */
@@ -688,7 +691,9 @@ int mpt_set_skin(MptContext* ctx, const int32_t* joints, const float* weights, i
  * mpt_update_vertices of mpt_skin_host's output.
  * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, when no skin is
  * set, num_joints differs from the table's, a matrix entry is not finite (checked on the host) or a
- * skinned coordinate of any vertex is not finite (the device's flag).  MPT_ERR_HIP part-way leaves
+ * skinned coordinate of any vertex is not finite (the device's flag); the joint records are
+ * uploaded into a staging buffer and kept only when the call is accepted.  With a morph set the call
+ * evaluates the retained morph weights first, in the fused kernel (below).  MPT_ERR_HIP part-way leaves
  * the context without a scene.  The reset rule and info are those of mpt_update_vertices; the refit
  * is always the GPU's.  Measuring aids, read from the environment at the call, the same bytes:
  * MPT_SKIN_GROUP=1 takes one vertex per lane instead of four, MPT_SKIN_LDS=0 gathers the palette
@@ -702,6 +707,76 @@ int mpt_update_skin(MptContext* ctx, const float* joint_matrices, int32_t num_jo
 int mpt_skin_host(const float* rest_vertices, const float* rest_normals_or_NULL, const int32_t* joints, const float* weights,
                   int32_t num_vertices, const float* joint_matrices, int32_t num_joints, float* out_vertices,
                   float* out_normals_or_NULL);
+/* Morph targets (DESIGN.md §2 "Geometry updates", Morph targets): blend shapes of the flat scene,
+ * applied BEFORE the skin as glTF does: pose = skin(morph(rest pose)).
+ * mpt_set_morph sets the tables once, sparse by target: target t of num_targets >= 1 owns the
+ * entries [target_offsets[t], target_offsets[t + 1]) of vertex_ids / pos_deltas / nrm_deltas (3
+ * floats per entry; nrm_deltas NULL: the morph has no normal deltas).  target_offsets starts at 0
+ * and never decreases (a target may be empty); the ids of a target are strictly ascending in
+ * [0, num_vertices), so a vertex appears at most once per target.  The library transposes the
+ * tables by vertex on the host (a stable counting sort, shared with mpt_morph_host: a vertex's
+ * entries end up in ascending target order) and uploads that form.
+ * STATE.  A morph composes with a skin and excludes an object table: mpt_set_morph drops an object
+ * table, mpt_set_objects drops a morph as it drops a skin (a rigid object is a one-joint skin).  A
+ * morph and a skin share one REST POSE and the staging arrays: whichever of the two is set first
+ * captures it as mpt_set_objects does, setting the second does not capture again, and it lives
+ * until both are gone -- mpt_set_skin(NULL) with a morph set frees only the skin's tables,
+ * mpt_set_morph(NULL tables, num_targets 0) with a skin set frees only the morph's; without the
+ * other, either frees the rest pose and the staging arrays too.  With no morph ever set every call
+ * behaves as it did before morphs existed.
+ * The context retains the last ACCEPTED morph weights (all zero after mpt_set_morph) and the last
+ * ACCEPTED joint palette ("not posed", i.e. no skin step, after mpt_set_skin).  mpt_update_morph
+ * evaluates new weights with the retained palette; mpt_update_skin with a morph set evaluates the
+ * retained weights with the new palette through the fused kernel; mpt_update_morph_skin sets both:
+ * one kernel, one refit.  A refused call changes nothing, the retained weights and palette
+ * included: new weights and records are uploaded into staging buffers and swapped in on acceptance.
+ * mpt_update_vertices, mpt_update_vertices_device and rebuilds leave rest pose, weights and palette
+ * alone; mpt_upload_scene and mpt_upload_scene_mode drop everything.
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, for a vertex count
+ * other than the scene's, num_targets < 1 with tables, offsets that do not start at 0 or that
+ * decrease, an id outside [0, num_vertices) or out of order, or a delta that is not finite. */
+int mpt_set_morph(MptContext* ctx, int32_t num_targets, const int32_t* target_offsets /* [T+1] */,
+                  const int32_t* vertex_ids /* [N] */, const float* pos_deltas /* [3N] */,
+                  const float* nrm_deltas_or_NULL /* [3N] */, int32_t num_vertices);
+/* The most targets whose weights the morph kernel stages in LDS (16 KiB); more are gathered through
+ * the cache.  Both give the same bytes. */
+#define MPT_MORPH_LDS_TARGETS 4096
+/* Evaluates the morph: weights is num_targets floats on the host, applied to the rest pose by a
+ * kernel (csrc/morph.h has the arithmetic, shared with mpt_morph_host byte for byte; fp32, no fma).
+ * Per vertex, over its entries in ascending target order, those whose weight is not +0 / -0:
+ *   position  acc = p; acc[r] = acc[r] + w*dp[r]          (the product rounded, then the sum)
+ *   normal    with normal deltas: t = n; t[r] = t[r] + w*dn[r]; t / |t| when (t0*t0 + t1*t1) + t2*t2
+ *             is positive and finite, else the rest normal.  Without normal deltas it passes through.
+ * A vertex without such an entry passes through byte for byte, so all-zero weights change no bit
+ * and report area_ratio 1.  When the skin has been posed, mptskin's skin_vertex (mpt_update_skin)
+ * follows in the same kernel on the morphed position and normal in registers: the morphed pose is
+ * never written to memory.
+ * The flow is mpt_update_skin's: streams drained, 4 bytes per target uploaded (plus 64 per joint),
+ * the kernel writes the staging arrays and reduces the largest |coordinate| over the vertices in
+ * use and a non-finite flag, two words are read back, the arrays are swapped in, and the refit and
+ * the tables follow -- with the same bytes as mpt_update_vertices of
+ * mpt_skin_host(mpt_morph_host(rest pose)), or of mpt_morph_host(rest pose) alone without a posed
+ * skin.
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing (retained weights
+ * and palette included), when no morph is set, num_targets differs from the tables', a weight is
+ * not finite, or an output coordinate is not finite (the device's flag); mpt_update_morph_skin
+ * also when no skin is set, num_joints differs or a matrix entry is not finite.  MPT_ERR_HIP
+ * part-way leaves the context without a scene.  Measuring aids, read from the environment at the
+ * call, the same bytes: the kernel takes one vertex per lane, the faster of the two as measured
+ * (DESIGN.md §4), MPT_MORPH_GROUP=4 takes four with 16-byte accesses (MPT_MORPH_GROUP=1 names the
+ * default); MPT_MORPH_LDS=0 stages nothing in LDS. */
+int mpt_update_morph(MptContext* ctx, const float* weights, int32_t num_targets, MptRefitInfo* info_or_NULL);
+int mpt_update_morph_skin(MptContext* ctx, const float* weights, int32_t num_targets,
+                          const float* joint_matrices, int32_t num_joints, MptRefitInfo* info_or_NULL);
+/* No device needed: the host loop of csrc/morph.h -- what mpt_update_morph writes for a rest pose,
+ * tables (in mpt_set_morph's form) and weights (rest_normals NULL: positions only, out_normals must
+ * then be NULL).  MPT_ERR_INVALID_ARGUMENT for a NULL array, num_vertices < 1, what mpt_set_morph
+ * refuses, a non-finite weight or a non-finite output coordinate; the outputs are then
+ * unspecified, the inputs untouched. */
+int mpt_morph_host(const float* rest_vertices, const float* rest_normals_or_NULL, int32_t num_vertices,
+                   int32_t num_targets, const int32_t* target_offsets, const int32_t* vertex_ids,
+                   const float* pos_deltas, const float* nrm_deltas_or_NULL, const float* weights,
+                   float* out_vertices, float* out_normals_or_NULL);
 /* Downloads a BVH of the context as the kernels read it: which 0 the scene's, 1 the light-hit
  * BVH's (counts of 0 when none is in use).  nodes: 80-byte Node8, tris: 48-byte TriRec records
  * (csrc/bvh8.h; mpt.abi.NODE8_DTYPE / TRIREC_DTYPE).  out_counts (optional): nodes, records,
