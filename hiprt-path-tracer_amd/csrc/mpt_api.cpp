@@ -210,6 +210,13 @@ struct MptContext {
     DBuf<float> morph_dpos, morph_dnrm, morph_w, morph_w_stage;
     bool skin_posed = false;
     DBuf<float4> skin_recs_stage;
+    // an animation clip (mpt_set_animation, anim.hip): the packed tables with their scratch on the
+    // device (anim: counts and section offsets; its blob is not kept), and the kernel's flag word.
+    // It drives the skin's joints, the morph's targets or both, and goes when either goes.
+    bool has_anim = false;
+    AnimPacked anim;
+    DBuf<unsigned char> anim_blob;
+    DBuf<uint32_t> anim_flag;
     int refit_host_loop = 0;              // test hook (MPT_REFIT_HOST): the refit by the host loop of refit.h
     int light_bvh = 1;                    // MPT_LIGHT_BVH at mpt_create: 0 = one closest-hit traversal per light-hit query
     bool light_bvh_ok = false;            // the light BVH matches the materials (else: the exact closest-hit path)
@@ -1214,8 +1221,16 @@ static int check_scene(const MptScene* s) {
     return MPT_OK;
 }
 
+// The animation freed: with the skin or the morph it drives, or by mpt_set_animation(NULL).
+static void drop_animation(MptContext* c) {
+    c->has_anim = false;
+    c->anim = AnimPacked();
+    release_all(c->anim_blob, c->anim_flag);
+}
+
 // The skin's tables and its retained palette freed (the rest pose stays).
 static void drop_skin_tables(MptContext* c) {
+    drop_animation(c);
     c->num_joints = -1;
     c->skin_posed = false;
     release_all(c->skin_joints, c->skin_weights, c->skin_recs, c->skin_recs_stage);
@@ -1223,6 +1238,7 @@ static void drop_skin_tables(MptContext* c) {
 
 // The morph's tables and its retained weights freed (the rest pose stays).
 static void drop_morph_tables(MptContext* c) {
+    drop_animation(c);
     c->num_targets = -1;
     release_all(c->morph_row, c->morph_tgt, c->morph_dpos, c->morph_dnrm, c->morph_w, c->morph_w_stage);
 }
@@ -1457,13 +1473,15 @@ hipError_t ensure_used_mask(MptContext* c) {
     return e;
 }
 
-// The two words a reduction of xform.hip left: the maximum's bits and the non-finite flag.
-hipError_t read_reduction(MptContext* c, float* max_abs, bool* bad) {
-    uint32_t w[2] = {0, 0};
+// The two words a reduction of xform.hip left: the maximum's bits and the non-finite flag; with
+// extra, that device word is read in the same synchronisation and ORed into the flag.
+hipError_t read_reduction(MptContext* c, float* max_abs, bool* bad, const uint32_t* extra = nullptr) {
+    uint32_t w[2] = {0, 0}, x = 0;
     hipError_t e = hipMemcpyAsync(w, c->xf_red.p, sizeof(w), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && extra) e = hipMemcpyAsync(&x, extra, sizeof(x), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     std::memcpy(max_abs, &w[0], 4);
-    *bad = w[1] != 0;
+    *bad = w[1] != 0 || x != 0;
     return e;
 }
 
@@ -1496,16 +1514,27 @@ bool morph_lds() {
     const char* e = std::getenv("MPT_MORPH_LDS");
     return !(e && e[0] == '0' && e[1] == 0);
 }
+// k_anim keeps the world matrices in LDS when they fit (MPT_ANIM_LDS=0: always in memory) --
+// tools/anim_time.py measures both
+bool anim_lds() {
+    const char* e = std::getenv("MPT_ANIM_LDS");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
 
 // The pose of a skin and / or a morph evaluated from the shared rest pose: what mpt_update_skin,
-// mpt_update_morph and mpt_update_morph_skin have in common once their arguments are checked.
-// weights (NULL: the retained ones) are the morph's num_targets weights, matrices (NULL: the
-// retained palette, if the skin has been posed) the skin's num_joints matrices.  Everything up to
-// the swap writes scratch only -- the new weights and records included -- so a refusal changes
-// nothing, retained state included.
-int update_pose(MptContext* c, const float* weights, const float* matrices, MptRefitInfo* info, const char* who) {
+// mpt_update_morph, mpt_update_morph_skin and mpt_update_animation have in common once their
+// arguments are checked.  weights (NULL: the retained ones) are the morph's num_targets weights,
+// matrices (NULL: the retained palette, if the skin has been posed) the skin's num_joints matrices.
+// anim_time (not NULL: both others NULL): the staged weights and records come from the device
+// instead, written by k_anim for the context's animation -- those of the two that it drives -- and
+// its flag is read with the reductions.  Everything up to the swap writes scratch only -- the new
+// weights and records included -- so a refusal changes nothing, retained state included.
+int update_pose(MptContext* c, const float* weights, const float* matrices, MptRefitInfo* info, const char* who,
+                const float* anim_time = nullptr) {
+    const bool new_w = weights || (anim_time && c->anim.T > 0);
+    const bool new_m = matrices || (anim_time && c->anim.J > 0);
     const bool morph = c->num_targets >= 0;
-    const bool skin = matrices || (c->num_joints >= 0 && c->skin_posed);
+    const bool skin = new_m || (c->num_joints >= 0 && c->skin_posed);
     const size_t nv = c->pos.n / 3;
     if (c->rest_pos.n != c->pos.n || c->rest_nrm.n != c->nrm.n) return fail(MPT_ERR_INVALID_ARGUMENT, "rest pose does not fit the scene");
     if (skin && (3 * c->skin_joints.n != 4 * c->pos.n || c->skin_weights.n != c->skin_joints.n))
@@ -1529,8 +1558,16 @@ int update_pose(MptContext* c, const float* weights, const float* matrices, MptR
     if (e == hipSuccess) e = c->xf_red.alloc(2);
     if (e == hipSuccess && matrices) e = c->skin_recs_stage.upload(recs.data(), recs.size(), st);
     if (e == hipSuccess && weights) e = c->morph_w_stage.upload(wpad.data(), wpad.size(), st);
-    const float4* d_recs = matrices ? c->skin_recs_stage.p : c->skin_recs.p;
-    const float* d_w = weights ? c->morph_w_stage.p : c->morph_w.p;
+    if (anim_time) {
+        // (a buffer the animation does not drive is not touched: k_anim's loop over it is empty)
+        if (e == hipSuccess && new_m) e = c->skin_recs_stage.alloc((size_t)(mptskin::REC / 4) * (size_t)c->anim.J);
+        if (e == hipSuccess && new_w) e = c->morph_w_stage.alloc(((size_t)c->anim.T + 3) / 4 * 4);
+        if (e == hipSuccess)
+            e = launch_anim(anim_tables(c->anim, c->anim_blob.p), *anim_time, c->skin_recs_stage.p, (float4*)c->morph_w_stage.p,
+                            c->anim_flag.p, anim_lds(), st);
+    }
+    const float4* d_recs = new_m ? c->skin_recs_stage.p : c->skin_recs.p;
+    const float* d_w = new_w ? c->morph_w_stage.p : c->morph_w.p;
     if (e == hipSuccess && !morph)
         e = launch_skin(c->rest_pos.p, c->rest_nrm.p, c->skin_joints.p, c->skin_weights.p, c->vert_used.p, (const float*)d_recs,
                         c->num_joints, (int)nv, c->stage_pos.p, c->stage_nrm.p, c->xf_red.p, skin_group(), skin_lds(), st);
@@ -1544,18 +1581,18 @@ int update_pose(MptContext* c, const float* weights, const float* matrices, MptR
         a.out_pos = c->stage_pos.p; a.out_nrm = c->stage_nrm.p; a.red = c->xf_red.p;
         e = launch_morph(a, morph_group(), morph_lds(), st);
     }
-    if (e == hipSuccess) e = read_reduction(c, &m, &bad);
+    if (e == hipSuccess) e = read_reduction(c, &m, &bad, anim_time ? c->anim_flag.p : nullptr);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         c->has_scene = false;
         return fail(MPT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     }
-    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
-    if (matrices) {
+    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, anim_time ? "non-finite animation value or vertex coordinate" : "non-finite vertex coordinate");
+    if (new_m) {
         std::swap(c->skin_recs.p, c->skin_recs_stage.p); std::swap(c->skin_recs.n, c->skin_recs_stage.n);
         c->skin_posed = true;
     }
-    if (weights) { std::swap(c->morph_w.p, c->morph_w_stage.p); std::swap(c->morph_w.n, c->morph_w_stage.n); }
+    if (new_w) { std::swap(c->morph_w.p, c->morph_w_stage.p); std::swap(c->morph_w.n, c->morph_w_stage.n); }
     std::swap(c->pos.p, c->stage_pos.p);
     std::swap(c->nrm.p, c->stage_nrm.p);
     const float pad = std::ldexp(std::max(m, 1.0f), -20);
@@ -1809,6 +1846,51 @@ int mpt_update_morph_skin(MptContext* c, const float* weights, int32_t num_targe
     if (!weights_finite(weights, num_targets)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite morph weight");
     if (!matrices_finite(joint_matrices, num_joints)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite matrix entry");
     return update_pose(c, weights, joint_matrices, info, "mpt_update_morph_skin");
+}
+
+int mpt_set_animation(MptContext* c, const MptAnimation* anim) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!anim) {
+        HIPCHK(hipSetDevice(c->device));
+        drop_animation(c);
+        return MPT_OK;
+    }
+    AnimPacked p;
+    if (const char* bad = pack_animation(*anim, p)) return fail(MPT_ERR_INVALID_ARGUMENT, bad);
+    if (p.J > 0 && c->num_joints < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: joints without a skin set");
+    if (p.J > 0 && p.J != c->num_joints) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: joint count differs from the skin's");
+    if (p.T > 0 && c->num_targets < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: targets without a morph set");
+    if (p.T > 0 && p.T != c->num_targets) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: target count differs from the morph's");
+    HIPCHK(hipSetDevice(c->device));
+    // into new buffers, swapped in when they are there: a failure leaves what was set
+    DBuf<unsigned char> db;
+    DBuf<uint32_t> df;
+    hipStream_t st = c->stream;
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = db.upload(p.blob.data(), p.blob.size(), st);
+    if (e == hipSuccess) e = df.alloc(1);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_animation: ") + hipGetErrorString(e));
+    }
+    drop_animation(c);
+    std::swap(c->anim_blob.p, db.p); std::swap(c->anim_blob.n, db.n);
+    std::swap(c->anim_flag.p, df.p); std::swap(c->anim_flag.n, df.n);
+    p.blob = std::vector<unsigned char>();   // (only the counts and the offsets are kept)
+    c->anim = std::move(p);
+    c->has_anim = true;
+    return MPT_OK;
+}
+
+int mpt_update_animation(MptContext* c, float time, MptRefitInfo* info) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->has_anim) return fail(MPT_ERR_INVALID_ARGUMENT, "no animation set");
+    if (!(std::fabs(time) <= FLT_MAX)) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: time not finite");
+    // (the animation goes with the skin and the morph it drives: the counts still fit)
+    return update_pose(c, nullptr, nullptr, info, "mpt_update_animation", &time);
 }
 
 int mpt_update_vertices_device(MptContext* c, const float* d_vertices, const float* d_normals, int32_t num_vertices,

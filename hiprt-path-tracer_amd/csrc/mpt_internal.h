@@ -10,6 +10,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
+#include "anim.h"
 #include "bvh8.h"
 #include "mpt.h"
 
@@ -469,6 +472,22 @@ struct MorphLaunch {
 };
 hipError_t launch_morph(const MorphLaunch& a, int group, bool lds, hipStream_t st);
 bool weights_finite(const float* w, int32_t n);
+// anim.hip (anim.h): an animation's tables, checked and packed with their scratch into one array of
+// 16-byte aligned sections (off: where each lies); anim_tables gives the pointers for a copy of the
+// array at base, on the host or on the device.  launch_anim evaluates the clip at time t with one
+// workgroup into recs (J 16-word records) and wout ((T + 3) / 4 float4: the weights, zero padded)
+// and leaves in *flag whether a value, weight or matrix entry was not finite; lds: world matrices in
+// LDS up to MPT_ANIM_LDS_NODES nodes.  animation_host is the host loop of the same arithmetic.
+struct AnimPacked {
+    static constexpr int SECTIONS = 22;
+    int32_t N = 0, J = 0, T = 0, S = 0, C = 0, levels = 0;
+    size_t off[SECTIONS] = {};
+    std::vector<unsigned char> blob;
+};
+const char* pack_animation(const MptAnimation& a, AnimPacked& out);
+mptanim::Tables anim_tables(const AnimPacked& p, unsigned char* base);
+hipError_t launch_anim(const mptanim::Tables& a, float t, float4* recs, float4* wout, uint32_t* flag, bool lds, hipStream_t st);
+bool animation_host(const mptanim::Tables& a, float t, float* out_matrices, float* out_weights);
 // the scene BVH as mpt_upload_scene builds it (rebuilt shallower while too deep for stack_limit
 // entries); returns the stack limit in force (MPT_BVH_MAX_STACK)
 int build_scene_bvh8(const float* vertices, const int32_t* indices, int32_t num_triangles, BVH8& out, int stack_limit);

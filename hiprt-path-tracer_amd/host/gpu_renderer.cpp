@@ -184,6 +184,20 @@ void GPURenderer::update_morph_skin(const float* weights, int32_t num_targets, c
     reset();
 }
 
+void GPURenderer::set_animation(const MptAnimation* anim) {
+    for (MptContext* c : m_ctxs) check(mpt_set_animation(c, anim));
+}
+
+void GPURenderer::update_animation(float time, MptRefitInfo* info) {
+    for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_update_animation(m_ctxs[k], time, k == 0 ? info : nullptr));
+    reset();
+}
+
+void GPURenderer::animation_host(const MptAnimation& anim, float time, float* out_matrices, float* out_weights) {
+    if (mpt_animation_host(&anim, time, out_matrices, out_weights) != MPT_OK)
+        throw std::runtime_error(std::string("libmpt: ") + mpt_last_error());
+}
+
 void GPURenderer::rebuild_bvh(MptRebuildInfo* info, int32_t mode) {
     for (size_t k = 0; k < m_ctxs.size(); k++) check(mpt_rebuild_bvh_mode(m_ctxs[k], mode, k == 0 ? info : nullptr));
     // (no reset: results do not depend on the tree)

@@ -162,6 +162,17 @@ public:
     void update_morph(const float* weights, int32_t num_targets, MptRefitInfo* info = nullptr);
     void update_morph_skin(const float* weights, int32_t num_targets, const float* joint_matrices, int32_t num_joints,
                            MptRefitInfo* info = nullptr);
+    // set_animation / update_animation (no counterpart in the reference): one glTF clip played on
+    // the device.  set_animation gives every context the tables (mpt_set_animation; NULL removes
+    // the animation); the skin of set_skin and / or the morph of set_morph that the clip drives
+    // must be set.  update_animation samples the clip at `time`, composes the hierarchy and poses
+    // morph and skin on every context's GPU: one float per context crosses the bus.  The
+    // accumulation restarts as after update_vertices.  info (optional): the first context's report.
+    // animation_host needs no device: the joint matrices (12 floats each) and weights that
+    // update_animation evaluates (mpt_animation_host); either output may be NULL.
+    void set_animation(const MptAnimation* anim_or_null);
+    void update_animation(float time, MptRefitInfo* info = nullptr);
+    static void animation_host(const MptAnimation& anim, float time, float* out_matrices_or_null, float* out_weights_or_null);
     // rebuild_bvh (no counterpart in the reference): every context rebuilds its BVHs on its GPU
     // from the positions it holds (mpt_rebuild_bvh_mode), e.g. once update_vertices reports a large
     // area_ratio.  The accumulation continues: traversal results do not depend on the tree.

@@ -23,7 +23,7 @@ from ._build import LIB_PATH
 
 __all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
            "display_host", "write_png", "denoise_host", "bvh_refit_host", "bvh_build_host", "transform_host", "skin_host",
-           "SKIN_LDS_JOINTS", "morph_host", "MORPH_LDS_TARGETS"]
+           "SKIN_LDS_JOINTS", "morph_host", "MORPH_LDS_TARGETS", "animation_tables", "animation_host", "ANIM_LDS_NODES"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -41,10 +41,12 @@ SYMBOLS = [
     "mpt_set_objects", "mpt_update_transforms", "mpt_update_vertices_device", "mpt_transform_host",
     "mpt_set_skin", "mpt_update_skin", "mpt_skin_host",
     "mpt_set_morph", "mpt_update_morph", "mpt_update_morph_skin", "mpt_morph_host",
+    "mpt_set_animation", "mpt_update_animation", "mpt_animation_host",
 ]
 
 SKIN_LDS_JOINTS = abi.SKIN_LDS_JOINTS
 MORPH_LDS_TARGETS = abi.MORPH_LDS_TARGETS
+ANIM_LDS_NODES = abi.ANIM_LDS_NODES
 
 
 class MptError(RuntimeError):
@@ -142,6 +144,9 @@ def lib() -> C.CDLL:
     L.mpt_update_morph.argtypes = [vp, vp, i32, C.POINTER(abi.RefitInfo)]
     L.mpt_update_morph_skin.argtypes = [vp, vp, i32, vp, i32, C.POINTER(abi.RefitInfo)]
     L.mpt_morph_host.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.mpt_set_animation.argtypes = [vp, C.POINTER(abi.Animation)]
+    L.mpt_update_animation.argtypes = [vp, C.c_float, C.POINTER(abi.RefitInfo)]
+    L.mpt_animation_host.argtypes = [C.POINTER(abi.Animation), C.c_float, vp, vp]
     _lib = L
     return L
 
@@ -460,6 +465,87 @@ def morph_host(rest_vertices, rest_normals, morph, weights):
     return ov, on
 
 
+_ANIM_INTERP = {"STEP": abi.ANIM_STEP, "LINEAR": abi.ANIM_LINEAR, "CUBICSPLINE": abi.ANIM_CUBICSPLINE}
+_ANIM_PATH = {"translation": abi.ANIM_PATH_TRANSLATION, "rotation": abi.ANIM_PATH_ROTATION, "scale": abi.ANIM_PATH_SCALE,
+              "weights": abi.ANIM_PATH_WEIGHTS}
+_ANIM_FIELDS = [("node_parents", np.int32), ("node_trs", np.float32), ("node_is_trs", np.uint8), ("node_locals", np.float64),
+                ("joint_nodes", np.int32), ("joint_bind", np.float64), ("base_weights", np.float32),
+                ("sampler_key_offsets", np.int32), ("key_times", np.float32), ("sampler_value_offsets", np.int32),
+                ("values", np.float32), ("sampler_interp", np.int32), ("channel_sampler", np.int32), ("channel_node", np.int32),
+                ("channel_path", np.int32), ("channel_first_target", np.int32), ("channel_num_targets", np.int32)]
+
+
+def animation_tables(sd, clip=0):
+    """The tables of MptAnimation for clip `clip` of a loaded glTF file (sd.animations, sd.nodes,
+    sd.skin, sd.morph), as a dict of numpy arrays named like the struct's fields: what
+    GPURenderer.set_animation and animation_host take, and what a caller may build by hand.
+    node_locals and joint_bind are [.., 3, 4] float64.  A weights channel's node is mapped to its
+    stretch of the target list through sd.morph.target_node, and the base weights are
+    sd.morph.default_weights.  Channels that nothing can drive -- weights of a node without targets
+    in sd.morph -- are left out."""
+    if not 0 <= clip < len(sd.animations):
+        raise ValueError(f"animation_tables: clip {clip} of {len(sd.animations)}")
+    ad, nt = sd.animations[clip], sd.nodes
+    t = {"node_parents": nt.parents, "node_trs": nt.trs, "node_is_trs": nt.is_trs, "node_locals": nt.locals[:, :3, :]}
+    if sd.skin is not None:
+        t["joint_nodes"], t["joint_bind"] = sd.skin.joint_nodes, sd.skin.bind[:, :3, :]
+    if sd.morph is not None:
+        t["base_weights"] = sd.morph.default_weights
+    koff, voff = [0], [0]
+    for sm in ad.samplers:
+        koff.append(koff[-1] + len(sm.times))
+        voff.append(voff[-1] + sm.values.size)
+    t["sampler_key_offsets"], t["sampler_value_offsets"] = koff, voff
+    t["key_times"] = np.concatenate([sm.times for sm in ad.samplers]) if ad.samplers else []
+    t["values"] = np.concatenate([sm.values.reshape(-1) for sm in ad.samplers]) if ad.samplers else []
+    t["sampler_interp"] = [_ANIM_INTERP[sm.interpolation] for sm in ad.samplers]
+    cs, cn, cp, c0, ck = [], [], [], [], []
+    for ch in ad.channels:
+        first, count = 0, 0
+        if ch.path == "weights":
+            own = np.nonzero(sd.morph.target_node == ch.node)[0] if sd.morph is not None else []
+            if len(own) == 0:
+                continue
+            first, count = int(own[0]), len(own)
+        cs.append(ch.sampler); cn.append(ch.node); cp.append(_ANIM_PATH[ch.path]); c0.append(first); ck.append(count)
+    t["channel_sampler"], t["channel_node"], t["channel_path"] = cs, cn, cp
+    t["channel_first_target"], t["channel_num_targets"] = c0, ck
+    return {k: np.ascontiguousarray(t.get(k, []), dt) for k, dt in _ANIM_FIELDS}
+
+
+def _animation_struct(tables, clip, who):
+    """(abi.Animation, the arrays it points to) from a SceneData or a dict as animation_tables gives."""
+    if isinstance(tables, scene.SceneData):
+        tables = animation_tables(tables, clip)
+    a = {k: np.ascontiguousarray(tables.get(k, []), dt) for k, dt in _ANIM_FIELDS}
+    N, J, T = len(a["node_parents"]), len(a["joint_nodes"]), len(a["base_weights"])
+    S, Cn = len(a["sampler_interp"]), len(a["channel_sampler"])
+    for k, n in (("node_trs", 10 * N), ("node_is_trs", N), ("node_locals", 12 * N), ("joint_bind", 12 * J),
+                 ("sampler_key_offsets", S + 1 if S else 0), ("sampler_value_offsets", S + 1 if S else 0),
+                 ("channel_node", Cn), ("channel_path", Cn), ("channel_first_target", Cn), ("channel_num_targets", Cn)):
+        if a[k].size != n:
+            raise ValueError(f"{who}: {k} has {a[k].size} entries, not {n}")
+    if S and (a["key_times"].size != a["sampler_key_offsets"][-1] or a["values"].size != a["sampler_value_offsets"][-1]):
+        raise ValueError(f"{who}: key_times / values do not have their offsets' last entry")
+    st = abi.Animation()
+    st.num_nodes, st.num_joints, st.num_targets, st.num_samplers, st.num_channels = N, J, T, S, Cn
+    for k, _ in _ANIM_FIELDS:
+        setattr(st, k, a[k].ctypes.data if a[k].size else None)
+    return st, a
+
+
+def animation_host(tables, t, clip=0):
+    """mpt_animation_host, no GPU: the host loop of csrc/anim.h -- what GPURenderer.update_animation(t)
+    evaluates for these tables (a SceneData with its clip number, or a dict as animation_tables
+    gives).  Returns (weights float32 [T] or None without targets, matrices float32 [J, 3, 4] or None
+    without joints): the arguments of update_morph_skin."""
+    st, keep = _animation_struct(tables, clip, "animation_host")
+    w = np.empty(st.num_targets, np.float32) if st.num_targets else None
+    m = np.empty((st.num_joints, 3, 4), np.float32) if st.num_joints else None
+    _check(lib().mpt_animation_host(C.byref(st), float(t), _p(m), _p(w)))
+    return w, m
+
+
 def _on_device(a):
     """A torch tensor in GPU memory (anything else, a CPU tensor included, is a host array)."""
     return bool(getattr(a, "is_cuda", False))
@@ -620,6 +706,27 @@ class GPURenderer:
         m = _matrices(matrices, "update_morph_skin")
         ri = abi.RefitInfo() if info else None
         _check(lib().mpt_update_morph_skin(self.h, _p(w), len(w), _p(m), len(m), C.byref(ri) if info else None))
+        return ri
+
+    def set_animation(self, tables, clip=0):
+        """mpt_set_animation: tables is a SceneData loaded from a glTF file (its clip number `clip`)
+        or a dict as mpt.animation_tables gives.  The skin and / or the morph that the clip drives
+        must be set, with as many joints and targets; setting either anew, set_objects and set_scene
+        drop the animation.  tables=None removes it."""
+        if tables is None:
+            _check(lib().mpt_set_animation(self.h, None))
+            return
+        st, keep = _animation_struct(tables, clip, "set_animation")
+        _check(lib().mpt_set_animation(self.h, C.byref(st)))
+
+    def update_animation(self, t, info=False):
+        """mpt_update_animation: the clip sampled at t seconds, the hierarchy composed and the joint
+        palette and morph weights written on the GPU, then the fused morph and skin kernel and the
+        refit of both BVHs: one float crosses the bus.  The same bytes as
+        update_morph_skin(*mpt.animation_host(tables, t)).  The next frame must carry
+        need_to_reset.  info=True returns the abi.RefitInfo, else None."""
+        ri = abi.RefitInfo() if info else None
+        _check(lib().mpt_update_animation(self.h, float(t), C.byref(ri) if info else None))
         return ri
 
     def rebuild_bvh(self, info=False, mode=abi.BUILD_LBVH):

@@ -463,6 +463,21 @@ class RefitInfo(C.Structure):
 BUILD_LBVH, BUILD_PLOC, BUILD_SAH = 0, 1, 3   # MPT_BUILD_*: the build modes of mpt_rebuild_bvh_mode (2 is none)
 SKIN_LDS_JOINTS = 256   # MPT_SKIN_LDS_JOINTS: the largest palette mpt_update_skin's kernel stages in LDS
 MORPH_LDS_TARGETS = 4096   # MPT_MORPH_LDS_TARGETS: the most morph weights the morph kernel stages in LDS
+ANIM_LDS_NODES = 512   # MPT_ANIM_LDS_NODES: the most nodes whose world matrices the animation kernel keeps in LDS
+ANIM_STEP, ANIM_LINEAR, ANIM_CUBICSPLINE = 0, 1, 2   # MPT_ANIM_*: a sampler's interpolation
+ANIM_PATH_TRANSLATION, ANIM_PATH_ROTATION, ANIM_PATH_SCALE, ANIM_PATH_WEIGHTS = 0, 1, 2, 3   # MPT_ANIM_PATH_*
+
+
+class Animation(C.Structure):
+    """MptAnimation: the tables of mpt_set_animation / mpt_animation_host (mpt.h)."""
+    _fields_ = [("num_nodes", i32), ("num_joints", i32), ("num_targets", i32), ("num_samplers", i32), ("num_channels", i32),
+                ("reserved", i32),
+                ("node_parents", C.c_void_p), ("node_trs", C.c_void_p), ("node_is_trs", C.c_void_p), ("node_locals", C.c_void_p),
+                ("joint_nodes", C.c_void_p), ("joint_bind", C.c_void_p), ("base_weights", C.c_void_p),
+                ("sampler_key_offsets", C.c_void_p), ("key_times", C.c_void_p), ("sampler_value_offsets", C.c_void_p),
+                ("values", C.c_void_p), ("sampler_interp", C.c_void_p),
+                ("channel_sampler", C.c_void_p), ("channel_node", C.c_void_p), ("channel_path", C.c_void_p),
+                ("channel_first_target", C.c_void_p), ("channel_num_targets", C.c_void_p)]
 
 
 class RebuildInfo(C.Structure):

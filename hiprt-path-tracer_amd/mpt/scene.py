@@ -101,6 +101,52 @@ class MorphData:
         return len(self.target_node)
 
 
+class AnimationSampler:
+    """One sampler of a clip: times float32 [K], values float32 [K, W] (CUBICSPLINE: [3K, W], per key
+    in-tangent, value, out-tangent; W = 3, 4 or the target count of a weights channel's mesh), the
+    normalised integer outputs converted by glTF's formulas, and interpolation, one of "STEP",
+    "LINEAR", "CUBICSPLINE"."""
+
+    def __init__(self, times, values, interpolation):
+        self.times = times
+        self.values = values
+        self.interpolation = interpolation
+
+
+class AnimationChannel:
+    """One channel of a clip: its sampler's index, the target node and the path, one of
+    "translation", "rotation", "scale", "weights"."""
+
+    def __init__(self, sampler, node, path):
+        self.sampler = sampler
+        self.node = node
+        self.path = path
+
+
+class AnimationData:
+    """One glTF animation (SceneData.animations): what mpt.animation_tables turns into the tables
+    of GPURenderer.set_animation and mpt.animation_host."""
+
+    def __init__(self):
+        self.name = ""
+        self.duration = 0.0    # the largest key time
+        self.samplers = []     # list[AnimationSampler]
+        self.channels = []     # list[AnimationChannel]
+
+
+class NodeTable:
+    """Every node of a glTF file (SceneData.nodes, present when the file has animations or a skin):
+    parents int32 [N] (-1: a root), trs float32 [N, 10] (translation, rotation x y z w, scale; the
+    identity TRS for a node given as a matrix), is_trs uint8 [N] (0: given as a `matrix`) and locals
+    float64 [N, 4, 4]."""
+
+    def __init__(self):
+        self.parents = None
+        self.trs = None
+        self.is_trs = None
+        self.locals = None
+
+
 def skin_matrices(sd, node_locals=None):
     """The joint matrices of a pose for GPURenderer.update_skin / mpt.skin_host: float32 [J, 3, 4],
     global_j @ sd.skin.bind[j], the global joint transforms recomputed in float64 from the file's
@@ -141,6 +187,8 @@ class SceneData:
         self.vertex_object = None     # int32 [V] or None: per vertex the ordinal of its mesh node (glTF loader)
         self.skin = None              # SkinData or None: the file's skinned mesh nodes (glTF loader)
         self.morph = None             # MorphData or None: the file's morph targets (glTF loader)
+        self.animations = []          # list[AnimationData]: the file's animations (glTF loader)
+        self.nodes = None             # NodeTable or None: every node, for files with animations or a skin (glTF loader)
         self.name = ""
 
     @property
@@ -617,6 +665,9 @@ def load_gltf(path, aspect_override=None):
         sd.morph = md
     sd.materials = mats
     sd.textures = textures
+    if pal_nodes or g.get("animations"):
+        sd.nodes = _node_table(g)
+    sd.animations = _load_animations(g, bins, os.path.basename(path))
 
     cams = [(ni, n) for ni, n in enumerate(g["nodes"]) if "camera" in n and ni in world]
     if cams:
@@ -630,6 +681,81 @@ def load_gltf(path, aspect_override=None):
                               hfov=p.get("yfov", 0.7) * (aspect if aspect != 0 else 1.0),
                               aspect=aspect, znear=p.get("znear", 0.1), zfar=p.get("zfar", 100.0))
     return sd.finalize()
+
+
+def _node_table(g):
+    nt = NodeTable()
+    N = len(g["nodes"])
+    nt.parents = np.full(N, -1, np.int32)
+    nt.trs = np.tile(np.array([0, 0, 0, 0, 0, 0, 1, 1, 1, 1], np.float32), (N, 1))
+    nt.is_trs = np.ones(N, np.uint8)
+    for ni, nd in enumerate(g["nodes"]):
+        for c in nd.get("children", []):
+            nt.parents[c] = ni
+        if "matrix" in nd:
+            nt.is_trs[ni] = 0
+        else:
+            nt.trs[ni, 0:3] = nd.get("translation", [0, 0, 0])
+            nt.trs[ni, 3:7] = nd.get("rotation", [0, 0, 0, 1])
+            nt.trs[ni, 7:10] = nd.get("scale", [1, 1, 1])
+    nt.locals = np.stack([_node_matrix(nd) for nd in g["nodes"]])
+    return nt
+
+
+_ANIM_WIDTH = {"translation": 3, "rotation": 4, "scale": 3}
+
+
+def _load_animations(g, bins, fname):
+    """glTF `animations` as a list of AnimationData.  ValueError, naming the file and the animation,
+    for a channel on a node given as a matrix, a weights channel on a node without morph targets,
+    an output count that does not match the key count, and two channels on one node and path.
+    Channels without a target node (KHR_animation_pointer) are left out; channels on nodes that
+    nothing here can drive (cameras, unskinned mesh nodes) load as they are."""
+    out = []
+    for ai, ga in enumerate(g.get("animations", [])):
+        who = f"{fname}: animation {ai} ({ga.get('name', '')!r})"
+        ad = AnimationData()
+        ad.name = ga.get("name", "")
+        widths = {}
+        seen = set()
+        for ch in ga.get("channels", []):
+            tg = ch.get("target", {})
+            if "node" not in tg or tg.get("path") not in ("translation", "rotation", "scale", "weights"):
+                continue
+            ni, path, si = int(tg["node"]), tg["path"], int(ch["sampler"])
+            if not 0 <= ni < len(g["nodes"]) or not 0 <= si < len(ga.get("samplers", [])):
+                raise ValueError(f"{who}: channel with node {ni}, sampler {si} out of range")
+            nd = g["nodes"][ni]
+            if "matrix" in nd:
+                raise ValueError(f"{who}: channel on node {ni}, which has a matrix")
+            if path == "weights":
+                prims = g["meshes"][nd["mesh"]]["primitives"] if "mesh" in nd else []
+                w = max([len(pr.get("targets", [])) for pr in prims], default=0)
+                if w == 0:
+                    raise ValueError(f"{who}: weights channel on node {ni}, which has no morph targets")
+            else:
+                w = _ANIM_WIDTH[path]
+            if (ni, path) in seen:
+                raise ValueError(f"{who}: two channels on node {ni}, path {path}")
+            seen.add((ni, path))
+            if widths.setdefault(si, w) != w:
+                raise ValueError(f"{who}: sampler {si} shared by channels of different widths")
+            ad.channels.append(AnimationChannel(si, ni, path))
+        for si, gs in enumerate(ga.get("samplers", [])):
+            times = np.ascontiguousarray(_accessor(g, bins, gs["input"]).reshape(-1), np.float32)
+            vals = _accessor(g, bins, gs["output"]).astype(np.float32)
+            interp = gs.get("interpolation", "LINEAR")
+            if interp not in ("STEP", "LINEAR", "CUBICSPLINE"):
+                raise ValueError(f"{who}: sampler {si}: interpolation {interp!r}")
+            w = widths.get(si, vals.shape[1])
+            rows = len(times) * (3 if interp == "CUBICSPLINE" else 1)
+            if len(times) < 1 or vals.size != rows * w:
+                raise ValueError(f"{who}: sampler {si}: {vals.size} output components for {len(times)} keys of width {w}"
+                                 + (" (CUBICSPLINE)" if interp == "CUBICSPLINE" else ""))
+            ad.samplers.append(AnimationSampler(times, np.ascontiguousarray(vals.reshape(rows, w)), interp))
+            ad.duration = max(ad.duration, float(times.max()))
+        out.append(ad)
+    return out
 
 
 def load_scene(name):

@@ -754,9 +754,25 @@ def write_morphed_gltf(path: str, skinned: bool = True, rings: int = 7, sides: i
     return _write_tube_gltf(path, rings, sides, 3, 1.8, 0.25, True, morph=True, skinned=skinned)
 
 
-def _write_tube_gltf(path, rings, sides, joints, length, radius, normalized_weights, morph=False, skinned=True):
+def write_animated_gltf(path: str, rings: int = 7, sides: int = 8) -> str:
+    """write_morphed_gltf's skinned scene with two animations.
+
+    * clip 0 "bend" (1.5 s): node 2 (the middle joint) has a LINEAR rotation with keys at 0, 0.5,
+      1.0 and 1.5 s, stored as normalised signed shorts -- the third key is the negated quaternion of
+      an 80 degree turn, so keys 1 and 2 have a negative dot product, and the fourth is one degree
+      further, so keys 2 and 3 lie above the slerp's lerp threshold -- and a STEP translation (keys
+      at 0, 0.6, 1.2); node 3 (the last joint) has a CUBICSPLINE rotation (keys at 0, 0.75, 1.5) and
+      a LINEAR scale (keys at 0.25 and 1.25); node 0 (the tube) has LINEAR weights for its two
+      targets (keys at 0, 0.7, 1.5).
+    * clip 1 "face" (2 s): CUBICSPLINE weights on node 0 (keys at 0, 1, 2) and a one-key LINEAR
+      translation of node 3."""
+    return _write_tube_gltf(path, rings, sides, 3, 1.8, 0.25, True, morph=True, skinned=True, animated=True)
+
+
+def _write_tube_gltf(path, rings, sides, joints, length, radius, normalized_weights, morph=False, skinned=True, animated=False):
     """The scene of write_skinned_gltf; morph: with write_morphed_gltf's two targets; skinned=False:
-    without the skin (the joint nodes stay in the file, unused)."""
+    without the skin (the joint nodes stay in the file, unused); animated: with
+    write_animated_gltf's two clips."""
     import base64
     import json
 
@@ -870,6 +886,49 @@ def _write_tube_gltf(path, rings, sides, joints, length, radius, normalized_weig
          "extensionsUsed": ["KHR_materials_emissive_strength"]}
     if not skinned:
         del g["skins"], nodes[0]["skin"]
+    if animated:
+        def rotz(deg, sign=1.0):
+            h = math.radians(deg) / 2.0
+            return [0.0, 0.0, sign * math.sin(h), sign * math.cos(h)]
+
+        def rotx(deg):
+            h = math.radians(deg) / 2.0
+            return [math.sin(h), 0.0, 0.0, math.cos(h)]
+
+        def sampler(times, values, interp, typ="VEC3", short=False):
+            v = np.asarray(values, np.float64)
+            if short:
+                out = acc(np.round(v * 32767.0).astype(np.int16), 5122, typ, True)
+            else:
+                out = acc(v.astype(np.float32), 5126, typ)
+            t = np.asarray(times, np.float32)
+            a = acc(t, 5126, "SCALAR")
+            accessors[a]["min"], accessors[a]["max"] = [float(t.min())], [float(t.max())]
+            return {"input": a, "output": out, "interpolation": interp}
+
+        def channel(si, node, pth):
+            return {"sampler": si, "target": {"node": node, "path": pth}}
+
+        z4 = [0.0, 0.0, 0.0, 0.0]
+        bend = [
+            sampler([0.0, 0.5, 1.0, 1.5], [rotz(0), rotz(40), rotz(80, -1.0), rotz(81, -1.0)], "LINEAR", "VEC4", short=True),
+            sampler([0.0, 0.75, 1.5], [z4, rotx(0), [0.4, 0.0, 0.0, -0.1], [0.3, 0.0, 0.1, 0.0], rotx(50), [0.2, 0.1, 0.0, 0.0],
+                                       [0.0, 0.2, 0.0, 0.1], rotx(-20), z4], "CUBICSPLINE", "VEC4"),
+            sampler([0.0, 0.6, 1.2], [[0.0, seg, 0.0], [0.05, seg, 0.0], [0.0, seg * 1.1, 0.05]], "STEP"),
+            sampler([0.25, 1.25], [[1.0, 1.0, 1.0], [1.2, 0.8, 1.1]], "LINEAR"),
+            sampler([0.0, 0.7, 1.5], np.array([0.25, 0.5, 1.0, 0.0, 0.1, 0.9]).reshape(-1, 1), "LINEAR", "SCALAR"),
+        ]
+        face_w = np.array([0.0, 0.0, 0.25, 0.5, 0.5, -0.3,   0.2, 0.1, 0.9, 0.1, -0.4, 0.6,   0.3, -0.2, 0.0, 1.0, 0.0, 0.0])
+        face = [sampler([0.0, 1.0, 2.0], face_w.reshape(-1, 1), "CUBICSPLINE", "SCALAR"),
+                sampler([0.5], [[0.02, seg, -0.03]], "LINEAR")]
+        g["animations"] = [
+            {"name": "bend", "samplers": bend,
+             "channels": [channel(0, 2, "rotation"), channel(1, 3, "rotation"), channel(2, 2, "translation"), channel(3, 3, "scale"),
+                          channel(4, 0, "weights")]},
+            {"name": "face", "samplers": face, "channels": [channel(0, 0, "weights"), channel(1, 3, "translation")]},
+        ]
+        binary = b"".join(chunks)
+        g["buffers"] = [{"byteLength": len(binary), "uri": "data:application/octet-stream;base64," + base64.b64encode(binary).decode()}]
     with open(path, "w") as f:
         json.dump(g, f)
     return path

@@ -777,6 +777,93 @@ int mpt_morph_host(const float* rest_vertices, const float* rest_normals_or_NULL
                    int32_t num_targets, const int32_t* target_offsets, const int32_t* vertex_ids,
                    const float* pos_deltas, const float* nrm_deltas_or_NULL, const float* weights,
                    float* out_vertices, float* out_normals_or_NULL);
+/* Animation clips (DESIGN.md §2 "Geometry updates", Animation): one glTF clip sampled, the node
+ * hierarchy composed and the joint palette and morph weights produced ON THE DEVICE, straight into
+ * the staging buffers the skin and morph kernels read: a frame of playback is one float.
+ * MptAnimation is counts and host pointers (csrc/anim.h's top comment is the specification):
+ *   nodes     node_parents [N] (-1: a root; a child may come before its parent), node_trs [10N]
+ *             (translation 3, rotation x y z w, scale 3), node_is_trs [N] (1: the node was given as
+ *             TRS and its local matrix is made from the sampled TRS; 0: given as a matrix, its
+ *             node_locals entry is used and no channel may drive it), node_locals [12N] row-major
+ *             3x4 float64
+ *   joints    joint_nodes [J], joint_bind [12J] row-major 3x4 float64; joint j's matrix is
+ *             world[joint_nodes[j]] * joint_bind[j] (two joints may share a node)
+ *   targets   base_weights [T]: what an undriven target keeps
+ *   samplers  sampler s owns the key times [sampler_key_offsets[s], sampler_key_offsets[s + 1]) of
+ *             key_times (at least one, finite, strictly ascending) and the floats
+ *             [sampler_value_offsets[s], sampler_value_offsets[s + 1]) of values: keys x width, x 3
+ *             for MPT_ANIM_CUBICSPLINE (in-tangent, value, out-tangent per key); both offset arrays
+ *             start at 0
+ *   channels  channel_sampler, channel_node, channel_path (MPT_ANIM_PATH_*), and for a weights
+ *             channel the stretch [channel_first_target, + channel_num_targets) of the weight
+ *             vector (the width of its values); no two channels write the same component
+ * mpt_set_animation checks the tables (check_animation), uploads them into a new buffer and swaps
+ * it in when it is there; NULL frees the animation.  num_joints > 0 needs a skin with as many
+ * joints, num_targets > 0 a morph with as many targets; one of the two must be driven.  It changes
+ * no geometry and no retained state.  The animation is dropped wherever a skin or a morph is
+ * dropped: mpt_set_objects, mpt_upload_scene*, mpt_set_skin / mpt_set_morph with new tables or NULL.
+ * One clip is set at a time.
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, for a count that
+ * does not fit the skin or the morph, a parent index out of range or a cycle, a joint or channel
+ * node out of range, offsets that decrease, key times that are not finite or not strictly
+ * ascending, a non-finite value, a stored rotation of zero length, a weights channel outside
+ * [0, T), a channel on a node given as a matrix, a value count that does not match the key count,
+ * or two channels that write the same component. */
+#define MPT_ANIM_STEP 0
+#define MPT_ANIM_LINEAR 1
+#define MPT_ANIM_CUBICSPLINE 2
+#define MPT_ANIM_PATH_TRANSLATION 0
+#define MPT_ANIM_PATH_ROTATION 1
+#define MPT_ANIM_PATH_SCALE 2
+#define MPT_ANIM_PATH_WEIGHTS 3
+typedef struct MptAnimation {
+    int32_t num_nodes;
+    int32_t num_joints;
+    int32_t num_targets;
+    int32_t num_samplers;
+    int32_t num_channels;
+    int32_t reserved;
+    const int32_t* node_parents;
+    const float* node_trs;
+    const uint8_t* node_is_trs;
+    const double* node_locals;
+    const int32_t* joint_nodes;
+    const double* joint_bind;
+    const float* base_weights;
+    const int32_t* sampler_key_offsets;
+    const float* key_times;
+    const int32_t* sampler_value_offsets;
+    const float* values;
+    const int32_t* sampler_interp;
+    const int32_t* channel_sampler;
+    const int32_t* channel_node;
+    const int32_t* channel_path;
+    const int32_t* channel_first_target;
+    const int32_t* channel_num_targets;
+} MptAnimation;
+int mpt_set_animation(MptContext* ctx, const MptAnimation* anim_or_NULL);
+/* The most nodes whose float64 world matrices the animation kernel keeps in LDS (96 bytes each,
+ * 48 KiB); more live in a scratch array in memory.  Both give the same bytes. */
+#define MPT_ANIM_LDS_NODES 512
+/* Evaluates the clip at `time` (seconds, clamped to every sampler's key range) with one workgroup
+ * (csrc/anim.hip: k_anim) -- channels sampled, local matrices made, world matrices composed level
+ * by level in float64, joint records and padded weights written to the staging buffers -- and then
+ * follows mpt_update_morph_skin's path with those buffers: the morph or skin kernel, ONE read of
+ * the reductions (the animation's non-finite flag in the same synchronisation), the swaps, the
+ * refit.  Nothing but `time` crosses the bus.  The result has the bytes mpt_update_morph_skin
+ * leaves for mpt_animation_host's output (mpt_update_skin / mpt_update_morph when only one of the
+ * two is driven).  On success the retained weights and palette are the evaluated ones.
+ * MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing (retained weights
+ * and palette included), when no animation is set, `time` is not finite, a sampled value, weight or
+ * matrix entry is not finite (the device's flag), or an output coordinate is not finite.
+ * Measuring aid, read from the environment at the call, the same bytes: MPT_ANIM_LDS=0 keeps the
+ * world matrices in memory whatever the node count. */
+int mpt_update_animation(MptContext* ctx, float time, MptRefitInfo* info_or_NULL);
+/* No device needed: the host loop of csrc/anim.h -- the joint matrices (num_joints x 12 floats) and
+ * weights (num_targets floats) mpt_update_animation evaluates for these tables at `time`; either
+ * output may be NULL.  MPT_ERR_INVALID_ARGUMENT for what mpt_set_animation refuses of the tables, a
+ * non-finite time or a non-finite result; the outputs are then unspecified. */
+int mpt_animation_host(const MptAnimation* anim, float time, float* out_matrices_or_NULL, float* out_weights_or_NULL);
 /* Downloads a BVH of the context as the kernels read it: which 0 the scene's, 1 the light-hit
  * BVH's (counts of 0 when none is in use).  nodes: 80-byte Node8, tris: 48-byte TriRec records
  * (csrc/bvh8.h; mpt.abi.NODE8_DTYPE / TRIREC_DTYPE).  out_counts (optional): nodes, records,
