@@ -20,6 +20,7 @@
 #include "denoise.h"
 #include "display.h"
 #include "morph.h"
+#include "normals.h"
 #include "mpt.h"
 #include "mpt_internal.h"
 #include "refit.h"
@@ -376,6 +377,13 @@ struct MptContext {
     // sample count it was made at (0: nothing denoised since the last resize)
     DBuf<float> den_scratch, den_out;
     int den_samples = 0;
+    // recomputed normals (mpt_set_normals, normals.hip): every vertex's group id, the by-group CSR
+    // of normals.h over the scene's indices, the groups' flip bytes and the face vectors' scratch
+    // array.  Independent of objects, skin, morph and animation; a scene upload drops it.
+    int num_groups = -1;                  // -1: normals are not recomputed
+    DBuf<int32_t> nrm_group, nrm_row, nrm_tri;
+    DBuf<uint8_t> nrm_flip;
+    DBuf<float4> nrm_face;
 };
 
 namespace {
@@ -1243,6 +1251,12 @@ static void drop_morph_tables(MptContext* c) {
     release_all(c->morph_row, c->morph_tgt, c->morph_dpos, c->morph_dnrm, c->morph_w, c->morph_w_stage);
 }
 
+// The state of mpt_set_normals freed: by mpt_set_normals(NULL) or a scene upload.
+static void drop_normals(MptContext* c) {
+    c->num_groups = -1;
+    release_all(c->nrm_group, c->nrm_row, c->nrm_tri, c->nrm_flip, c->nrm_face);
+}
+
 // The object table of mpt_set_objects, or the skin of mpt_set_skin and the morph of mpt_set_morph
 // (a table excludes the other two), the rest pose and the staging arrays freed.
 static void drop_objects(MptContext* c) {
@@ -1264,6 +1278,7 @@ static void take_scene_mirrors(MptContext* c, const MptScene* s) {
     c->nodes_light.release();
     c->tris_light.release();
     drop_objects(c);          // a new scene: the objects or the skin and the rest pose were the old one's
+    drop_normals(c);          // (its table was made over the old scene's indices)
     c->vert_used.release();
 }
 
@@ -1383,6 +1398,14 @@ hipError_t upload_vertices(MptContext* c, const float* v, const float* nrm) {
     return e;
 }
 
+// Which of normals.hip's two structures recomputes the normals: the two kernels by default, by the
+// measurement of DESIGN.md §4; MPT_NORMALS_FUSED=1 in the environment at the call, the one kernel
+// (tools/normals_time.py measures both)
+bool normals_fused() {
+    const char* e = std::getenv("MPT_NORMALS_FUSED");
+    return e && std::atoi(e) == 1;
+}
+
 // The tail of every geometry update, once pos / nrm hold the new arrays on the device: the refit
 // of both trees and the tables derived from the positions.  host_v: the same positions on the host
 // for the MPT_REFIT_HOST test hook (NULL: always the kernels -- mpt_update_transforms and
@@ -1423,6 +1446,18 @@ hipError_t refit_and_tables(MptContext* c, float pad, const float* host_v) {
             UV(launch_refit_levels(c->nodes_light.p, c->nbox_light.p, c->tbox.p, c->bvh_light.level_begin.data(),
                                    c->bvh_light.depth, st));
         }
+    }
+    // recomputed normals (mpt_set_normals): pos is read, nrm is rewritten in place for the grouped
+    // vertices, on the stream, before the attribute records bake the normals in
+    if (c->num_groups >= 0) {
+        NormalsLaunch a{};
+        a.idx = c->idx.p; a.pos = c->pos.p; a.num_tris = (int)(c->idx.n / 3);
+        a.group = c->nrm_group.p; a.has_n = c->has_n.p; a.row = c->nrm_row.p; a.tri = c->nrm_tri.p; a.flip = c->nrm_flip.p;
+        a.n = (int)c->nrm_group.n; a.nrm = c->nrm.p;
+        const bool fused = normals_fused();
+        if (!fused) UV(c->nrm_face.alloc(std::max(c->idx.n / 3, (size_t)1)));
+        a.face = c->nrm_face.p;
+        UV(launch_normals(a, fused, st));
     }
     UV(launch_tri_attr(dev_scene(c), c->tri_attr.p, st));
     // the emissive-triangle table holds positions (the materials' resolution comes out as it was)
@@ -1821,6 +1856,65 @@ int mpt_set_morph(MptContext* c, int32_t num_targets, const int32_t* target_offs
     std::swap(c->morph_dnrm.p, dn.p); std::swap(c->morph_dnrm.n, dn.n);
     std::swap(c->morph_w.p, dw.p); std::swap(c->morph_w.n, dw.n);
     c->num_targets = num_targets;
+    return MPT_OK;
+}
+
+int mpt_set_normals(MptContext* c, const int32_t* vertex_group, const uint8_t* group_flip, int32_t num_vertices, int32_t num_groups) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!vertex_group) {
+        if (num_groups != 0 || group_flip) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(drain(c));
+        drop_normals(c);
+        return MPT_OK;
+    }
+    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
+    // (the indices: the context's own copy, taken at the upload -- no update, rebuild or material
+    // edit changes them, so the copy is current also where the other host mirrors are stale)
+    if (3 * (c->h_idx.size() / 3) != c->h_idx.size() || c->h_idx.size() != c->idx.n)
+        return fail(MPT_ERR_HIP, "mpt_set_normals: index mirror differs from the scene's");
+    mptnormals::Csr csr;
+    if (const char* bad = mptnormals::to_csr(vertex_group, num_vertices, num_groups, c->h_idx.data(), (int32_t)(c->h_idx.size() / 3), csr))
+        return fail(MPT_ERR_INVALID_ARGUMENT, bad);
+    const std::vector<uint8_t> zeros(group_flip ? 0 : (size_t)num_groups, 0);
+    HIPCHK(hipSetDevice(c->device));
+    // into new buffers, swapped in when all of them are there: a failure leaves what was set
+    const size_t N = csr.tri.size();
+    DBuf<int32_t> dg, dr, dt;
+    DBuf<uint8_t> df;
+    hipStream_t st = c->stream;
+    hipError_t e = drain(c);
+    if (e == hipSuccess) e = dg.upload(vertex_group, (size_t)num_vertices, st);
+    if (e == hipSuccess) e = dr.upload(csr.row.data(), csr.row.size(), st);
+    // (a kernel is never handed a NULL table: groups without entries keep one unread entry)
+    if (e == hipSuccess) e = dt.alloc(std::max(N, (size_t)1));
+    if (e == hipSuccess && N) e = hipMemcpyAsync(dt.p, csr.tri.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = df.upload(group_flip ? group_flip : zeros.data(), (size_t)num_groups, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_normals: ") + hipGetErrorString(e));
+    }
+    drop_normals(c);
+    std::swap(c->nrm_group.p, dg.p); std::swap(c->nrm_group.n, dg.n);
+    std::swap(c->nrm_row.p, dr.p); std::swap(c->nrm_row.n, dr.n);
+    std::swap(c->nrm_tri.p, dt.p); std::swap(c->nrm_tri.n, dt.n);
+    std::swap(c->nrm_flip.p, df.p); std::swap(c->nrm_flip.n, df.n);
+    c->num_groups = num_groups;
+    return MPT_OK;
+}
+
+int mpt_get_vertices(MptContext* c, float* out_vertices, float* out_normals, int32_t num_vertices) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(drain(c));
+    if (out_vertices) HIPCHK(hipMemcpy(out_vertices, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_normals) HIPCHK(hipMemcpy(out_normals, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToHost));
     return MPT_OK;
 }
 

@@ -472,6 +472,25 @@ struct MorphLaunch {
 };
 hipError_t launch_morph(const MorphLaunch& a, int group, bool lds, hipStream_t st);
 bool weights_finite(const float* w, int32_t n);
+// normals.hip (normals.h): the normals of the n vertices with a group id >= 0 and a has_n byte
+// recomputed in place from pos and the num_tris triangles of idx through the by-group CSR (row:
+// num_groups + 1 offsets; tri per entry; flip: one byte per group).  fused: one kernel that forms
+// the face vectors in registers; else one kernel writes them to face (num_tris float4) and a second
+// gathers them.  Both give the same bytes.
+struct NormalsLaunch {
+    const int32_t* idx;
+    const float* pos;
+    int num_tris;
+    const int32_t* group;
+    const uint8_t* has_n;
+    const int32_t* row;
+    const int32_t* tri;
+    const uint8_t* flip;
+    int n;
+    float* nrm;
+    float4* face;
+};
+hipError_t launch_normals(const NormalsLaunch& a, bool fused, hipStream_t st);
 // anim.hip (anim.h): an animation's tables, checked and packed with their scratch into one array of
 // 16-byte aligned sections (off: where each lies); anim_tables gives the pointers for a copy of the
 // array at base, on the host or on the device.  launch_anim evaluates the clip at time t with one

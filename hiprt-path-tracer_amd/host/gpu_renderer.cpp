@@ -184,6 +184,14 @@ void GPURenderer::update_morph_skin(const float* weights, int32_t num_targets, c
     reset();
 }
 
+void GPURenderer::set_normals(const int32_t* vertex_group, const uint8_t* group_flip, int32_t num_vertices, int32_t num_groups) {
+    for (MptContext* c : m_ctxs) check(mpt_set_normals(c, vertex_group, group_flip, num_vertices, num_groups));
+}
+
+void GPURenderer::get_vertices(float* out_vertices, float* out_normals, int32_t num_vertices, int index) {
+    check(mpt_get_vertices(m_ctxs.at((size_t)index), out_vertices, out_normals, num_vertices));
+}
+
 void GPURenderer::set_animation(const MptAnimation* anim) {
     for (MptContext* c : m_ctxs) check(mpt_set_animation(c, anim));
 }

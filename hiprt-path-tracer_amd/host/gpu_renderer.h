@@ -173,6 +173,15 @@ public:
     void set_animation(const MptAnimation* anim_or_null);
     void update_animation(float time, MptRefitInfo* info = nullptr);
     static void animation_host(const MptAnimation& anim, float time, float* out_matrices_or_null, float* out_weights_or_null);
+    // set_normals / get_vertices (no counterpart in the reference): recomputed normals.  set_normals
+    // gives every context the smoothing groups (mpt_set_normals: one id in [-1, num_groups) per
+    // vertex, optional flip bytes per group; NULL with 0 groups removes them); from then on every
+    // geometry update above ends with the grouped vertices' normals recomputed from the new
+    // positions on every context's GPU.  Independent of objects, skin, morph and animation;
+    // set_scene drops it.  get_vertices downloads context `index`'s current positions and normals
+    // ([3V] floats each; either may be NULL).
+    void set_normals(const int32_t* vertex_group, const uint8_t* group_flip_or_null, int32_t num_vertices, int32_t num_groups);
+    void get_vertices(float* out_vertices_or_null, float* out_normals_or_null, int32_t num_vertices, int index = 0);
     // rebuild_bvh (no counterpart in the reference): every context rebuilds its BVHs on its GPU
     // from the positions it holds (mpt_rebuild_bvh_mode), e.g. once update_vertices reports a large
     // area_ratio.  The accumulation continues: traversal results do not depend on the tree.

@@ -23,7 +23,8 @@ from ._build import LIB_PATH
 
 __all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
            "display_host", "write_png", "denoise_host", "bvh_refit_host", "bvh_build_host", "transform_host", "skin_host",
-           "SKIN_LDS_JOINTS", "morph_host", "MORPH_LDS_TARGETS", "animation_tables", "animation_host", "ANIM_LDS_NODES"]
+           "SKIN_LDS_JOINTS", "morph_host", "MORPH_LDS_TARGETS", "animation_tables", "animation_host", "ANIM_LDS_NODES",
+           "normal_groups", "normal_flips", "normals_host"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -42,6 +43,7 @@ SYMBOLS = [
     "mpt_set_skin", "mpt_update_skin", "mpt_skin_host",
     "mpt_set_morph", "mpt_update_morph", "mpt_update_morph_skin", "mpt_morph_host",
     "mpt_set_animation", "mpt_update_animation", "mpt_animation_host",
+    "mpt_set_normals", "mpt_normals_host", "mpt_get_vertices",
 ]
 
 SKIN_LDS_JOINTS = abi.SKIN_LDS_JOINTS
@@ -147,6 +149,9 @@ def lib() -> C.CDLL:
     L.mpt_set_animation.argtypes = [vp, C.POINTER(abi.Animation)]
     L.mpt_update_animation.argtypes = [vp, C.c_float, C.POINTER(abi.RefitInfo)]
     L.mpt_animation_host.argtypes = [C.POINTER(abi.Animation), C.c_float, vp, vp]
+    L.mpt_set_normals.argtypes = [vp, vp, vp, i32, i32]
+    L.mpt_normals_host.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp]
+    L.mpt_get_vertices.argtypes = [vp, vp, vp, i32]
     _lib = L
     return L
 
@@ -465,6 +470,115 @@ def morph_host(rest_vertices, rest_normals, morph, weights):
     return ov, on
 
 
+def _scene_arrays(sd_or_arrays, who):
+    """A scene.SceneData, or (vertices, normals, indices[, has_normals]) -> contiguous float32 [V, 3]
+    positions and normals, int32 [3T] indices and uint8 [V] normal flags (None: every vertex has one)."""
+    if isinstance(sd_or_arrays, scene.SceneData):
+        sd = sd_or_arrays
+        parts = (sd.vertices, sd.normals, sd.triangle_indices, sd.has_normals)
+    else:
+        parts = tuple(sd_or_arrays)
+        if len(parts) not in (3, 4):
+            raise ValueError(f"{who}: a SceneData or (vertices, normals, indices[, has_normals]), not {len(parts)} arrays")
+        parts = parts + (None,) * (4 - len(parts))
+    v = np.ascontiguousarray(parts[0], np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(parts[1], np.float32).reshape(-1, 3)
+    if n.shape != v.shape:
+        raise ValueError(f"{who}: {n.shape[0]} normals for {v.shape[0]} vertices")
+    idx = np.ascontiguousarray(parts[2], np.int32).reshape(-1)
+    if len(idx) % 3:
+        raise ValueError(f"{who}: {len(idx)} indices are no whole number of triangles")
+    hn = None if parts[3] is None else np.ascontiguousarray(parts[3], np.uint8).reshape(-1)
+    if hn is not None and len(hn) != len(v):
+        raise ValueError(f"{who}: {len(hn)} normal flags for {len(v)} vertices")
+    return v, n, idx, hn
+
+
+def normal_groups(vertices, normals=None, only=None, weld=True):
+    """The smoothing groups for GPURenderer.set_normals / mpt.normals_host, numpy only: returns
+    (vertex_group int32 [V], num_groups).  vertices may be a scene.SceneData (its normals are then
+    used).  weld=True: vertices whose position AND normal are bitwise equal share a group, which
+    smooths across the splits that glTF needs at UV seams and keeps authored hard edges (their
+    normals differ).  weld=False: every vertex is its own group.  only: a mask [V]; the vertices
+    outside it get -1 and are never touched.  Groups are numbered in the order of their first
+    vertex."""
+    if isinstance(vertices, scene.SceneData):
+        vertices, normals = vertices.vertices, vertices.normals
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    V = len(v)
+    mask = np.ones(V, bool) if only is None else np.asarray(only, bool).reshape(-1)
+    if len(mask) != V:
+        raise ValueError(f"normal_groups: a mask of {len(mask)} for {V} vertices")
+    sel = np.nonzero(mask)[0]
+    group = np.full(V, -1, np.int32)
+    if weld:
+        if normals is None:
+            raise ValueError("normal_groups: weld=True needs the normals")
+        n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError(f"normal_groups: {n.shape[0]} normals for {V} vertices")
+        keys = np.concatenate([v[sel], n[sel]], axis=1).view(np.uint32).reshape(len(sel), 6)
+        _, first, inv = np.unique(keys, axis=0, return_index=True, return_inverse=True)
+        inv = np.asarray(inv).reshape(-1)
+        order = np.argsort(first, kind="stable")          # number the groups by their first vertex
+        rank = np.empty(len(first), np.int64)
+        rank[order] = np.arange(len(first))
+        group[sel] = rank[inv].astype(np.int32)
+        return group, int(len(first))
+    group[sel] = np.arange(len(sel), dtype=np.int32)
+    return group, int(len(sel))
+
+
+def normals_host(vertices, indices, vertex_group, normals, flips=None, num_groups=None, has_normals=None):
+    """mpt_normals_host, no GPU: the host loop of csrc/normals.h -- the vertex normals ([V, 3]
+    float32, a new array) that an update leaves on the device after GPURenderer.set_normals(
+    vertex_group, flips), for these positions, indices (int32 [3T]) and the normals the update itself
+    produced (kept by the vertices of group -1, by vertices whose has_normals byte is 0 and wherever
+    a group's sum has no positive finite length)."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    n = np.array(normals, np.float32, order="C").reshape(-1, 3)
+    if n.shape != v.shape:
+        raise ValueError(f"normals_host: {n.shape[0]} normals for {v.shape[0]} vertices")
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+    if len(idx) % 3:
+        raise ValueError(f"normals_host: {len(idx)} indices are no whole number of triangles")
+    g, f, G = _normal_table(vertex_group, flips, num_groups, "normals_host")
+    if len(g) != len(v):
+        raise ValueError(f"normals_host: {len(g)} group ids for {len(v)} vertices")
+    hn = None if has_normals is None else np.ascontiguousarray(has_normals, np.uint8).reshape(-1)
+    if hn is not None and len(hn) != len(v):
+        raise ValueError(f"normals_host: {len(hn)} normal flags for {len(v)} vertices")
+    _check(lib().mpt_normals_host(_p(v), len(v), _p(idx), len(idx) // 3, _p(g), _p(f), G, _p(hn), _p(n)))
+    return n
+
+
+def _normal_table(vertex_group, flips, num_groups, who):
+    g = np.ascontiguousarray(vertex_group, np.int32).reshape(-1)
+    G = (int(g.max()) + 1 if len(g) else 0) if num_groups is None else int(num_groups)
+    f = None if flips is None else np.ascontiguousarray(flips, np.uint8).reshape(-1)
+    if f is not None and len(f) != G:
+        raise ValueError(f"{who}: {len(f)} flip bytes for {G} groups")
+    return g, f, G
+
+
+def normal_flips(sd_or_arrays, vertex_group, num_groups):
+    """The flip bytes (uint8 [num_groups]) for GPURenderer.set_normals: normals_host runs on the
+    given pose -- a scene.SceneData or (vertices, normals, indices[, has_normals]) -- without flips,
+    and every group whose result has a negative dot product with the authored normal of the group's
+    first vertex gets its byte set.  For meshes whose winding was mirrored when the loader flattened
+    a node with a negative determinant."""
+    v, n, idx, hn = _scene_arrays(sd_or_arrays, "normal_flips")
+    g, _, G = _normal_table(vertex_group, None, num_groups, "normal_flips")
+    r = normals_host(v, idx, g, n, None, G, hn)
+    flips = np.zeros(G, np.uint8)
+    ids = np.nonzero(g >= 0)[0]
+    _, first = np.unique(g[ids], return_index=True)
+    fv = ids[first]                                        # the first vertex of every group that has one
+    dot = np.einsum("ij,ij->i", r[fv].astype(np.float64), n[fv].astype(np.float64))
+    flips[g[fv]] = dot < 0
+    return flips
+
+
 _ANIM_INTERP = {"STEP": abi.ANIM_STEP, "LINEAR": abi.ANIM_LINEAR, "CUBICSPLINE": abi.ANIM_CUBICSPLINE}
 _ANIM_PATH = {"translation": abi.ANIM_PATH_TRANSLATION, "rotation": abi.ANIM_PATH_ROTATION, "scale": abi.ANIM_PATH_SCALE,
               "weights": abi.ANIM_PATH_WEIGHTS}
@@ -688,6 +802,30 @@ class GPURenderer:
         T, off, ids, dp, dn = _morph_tables(morph, "set_morph")
         # (the tables do not say how many vertices the scene has: set_scene's count)
         _check(lib().mpt_set_morph(self.h, T, _p(off), _p(ids), _p(dp), _p(dn), self._n_verts))
+
+    def set_normals(self, vertex_group, flips=None, num_groups=None):
+        """mpt_set_normals: from now on every geometry update (update_vertices, update_transforms,
+        update_skin, update_morph, update_morph_skin, update_animation) ends with the smooth normals
+        of the grouped vertices recomputed from the new positions on the GPU -- area-weighted sums
+        of the face vectors per group, csrc/normals.h.  vertex_group is int32 [V] in [-1,
+        num_groups) (mpt.normal_groups makes it; -1: never touched; num_groups=None: the largest id
+        + 1), flips uint8 [num_groups] or None (mpt.normal_flips).  The call changes no normal
+        itself.  Normals given to update_vertices are overwritten for the grouped vertices.
+        Independent of objects, skin, morph and animation; set_scene drops it.
+        vertex_group=None removes it."""
+        if vertex_group is None:
+            _check(lib().mpt_set_normals(self.h, None, None, 0, 0))
+            return
+        g, f, G = _normal_table(vertex_group, flips, num_groups, "set_normals")
+        _check(lib().mpt_set_normals(self.h, _p(g), _p(f), len(g), G))
+
+    def get_vertices(self):
+        """mpt_get_vertices: (positions, normals), float32 [V, 3] each -- what the last update left
+        on the device, downloaded with the streams drained."""
+        v = np.empty((self._n_verts, 3), np.float32)
+        n = np.empty((self._n_verts, 3), np.float32)
+        _check(lib().mpt_get_vertices(self.h, _p(v), _p(n), self._n_verts))
+        return v, n
 
     def update_morph(self, weights, info=False):
         """mpt_update_morph: one weight per target ([T] float32) applied to the rest pose on the

@@ -95,10 +95,21 @@ class MorphData:
         self.target_node = None      # int32 [T]: the mesh node of every target
         self.target_index = None     # int32 [T]: its index among that node's mesh's targets
         self.default_weights = None  # float32 [T]: node.weights, else mesh.weights, else 0
+        self.num_vertices = None     # the scene's vertex count (the loader sets it): the length of touched
 
     @property
     def num_targets(self):
         return len(self.target_node)
+
+    @property
+    def touched(self):
+        """bool [V]: the vertices in any target -- the `only` mask of mpt.normal_groups for a file
+        whose targets have no NORMAL deltas (GPURenderer.set_normals)."""
+        if self.num_vertices is None:
+            raise ValueError("MorphData.touched: num_vertices is not set")
+        m = np.zeros(int(self.num_vertices), bool)
+        m[np.asarray(self.vertex_ids, np.int64)] = True
+        return m
 
 
 class AnimationSampler:
@@ -662,6 +673,7 @@ def load_gltf(path, aspect_override=None):
         md.target_node = np.array(tgt_node, np.int32)
         md.target_index = np.array(tgt_index, np.int32)
         md.default_weights = np.array(tgt_weight, np.float32)
+        md.num_vertices = len(sd.vertices)
         sd.morph = md
     sd.materials = mats
     sd.textures = textures

@@ -777,6 +777,55 @@ int mpt_morph_host(const float* rest_vertices, const float* rest_normals_or_NULL
                    int32_t num_targets, const int32_t* target_offsets, const int32_t* vertex_ids,
                    const float* pos_deltas, const float* nrm_deltas_or_NULL, const float* weights,
                    float* out_vertices, float* out_normals_or_NULL);
+/* Recomputed normals (DESIGN.md §2 "Geometry updates", Normals): an opt-in state of the context.
+ * Once set, EVERY geometry update -- mpt_update_vertices, mpt_update_vertices_device,
+ * mpt_update_transforms, mpt_update_skin, mpt_update_morph, mpt_update_morph_skin and
+ * mpt_update_animation -- ends with the smooth normals of the chosen vertices recomputed from the
+ * new positions on the device, before the per-triangle attribute records are made.  The call itself
+ * changes no normal; the next update does.  A context that never sets it behaves as before.
+ *   vertex_group [V]  values in [-1, num_groups): the vertices with one id form a smoothing group
+ *                     and receive one common normal; -1: the vertex is never touched
+ *   group_flip [G]    optional, one byte per group: non-zero negates the group's sum (a mesh whose
+ *                     winding was mirrored)
+ * csrc/normals.h has the arithmetic, shared with mpt_normals_host byte for byte (fp32, no fma):
+ *   table   by group, one entry (the triangle id p) for every corner (p, k) of the scene's index
+ *           buffer whose vertex lies in the group, in ascending p, then k (a stable counting sort on
+ *           the host; a triangle with two corners in one group appears twice)
+ *   face    e1 = b - a, e2 = c - a, f = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x),
+ *           every product rounded before the difference
+ *   sum     s = +0; s[r] = s[r] + f[r] over the group's entries in table order (area weighting);
+ *           s = -s when the group's flip byte is set
+ *   output  for every vertex v of the group with has_vertex_normals[v] != 0: s / sqrtf(l2) when
+ *           l2 = (s0*s0 + s1*s1) + s2*s2 is positive and finite, else the normal the update itself
+ *           left at v (the uploaded or deformed one): an empty group, a group of degenerate
+ *           triangles and an overflowing cross product pass through, and no update is refused
+ *           because of the recompute
+ * Vertices of group -1 and vertices without has_vertex_normals keep their bytes (the renderer shades
+ * the latter with the geometric normal).  Normals passed to mpt_update_vertices are uploaded first and
+ * then overwritten for the grouped vertices.
+ * The indices are the context's own copy of the scene's.  The tables are uploaded into new buffers
+ * and swapped in on success.  vertex_group NULL with num_groups 0 (and group_flip NULL) frees the
+ * state.  It is independent of objects, skin, morph and animation: none of them drops it and it drops
+ * none of them; rebuilds and material edits leave it; mpt_upload_scene and mpt_upload_scene_mode drop
+ * it.  MPT_ERR_NO_SCENE without a scene; MPT_ERR_INVALID_ARGUMENT, changing nothing, for a vertex
+ * count other than the scene's, num_groups < 1 with a table, or an id outside [-1, num_groups).
+ * Measuring aid, read from the environment at each update, the same bytes: by default one kernel
+ * writes the face vectors (16 bytes per triangle) and a second gathers them per vertex;
+ * MPT_NORMALS_FUSED=1 forms them in registers in one kernel. */
+int mpt_set_normals(MptContext* ctx, const int32_t* vertex_group, const uint8_t* group_flip_or_NULL,
+                    int32_t num_vertices, int32_t num_groups);
+/* No device needed: the host loop of csrc/normals.h -- the normals that an update leaves on the
+ * device after mpt_set_normals, for these positions, indices and groups, written over inout_normals
+ * (has_vertex_normals NULL: every vertex has one).  MPT_ERR_INVALID_ARGUMENT, the arrays untouched,
+ * for a NULL array, num_vertices < 1, num_triangles < 0, a vertex index outside [0, num_vertices),
+ * and what mpt_set_normals refuses. */
+int mpt_normals_host(const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_triangles,
+                     const int32_t* vertex_group, const uint8_t* group_flip_or_NULL, int32_t num_groups,
+                     const uint8_t* has_vertex_normals_or_NULL, float* inout_normals);
+/* Downloads the context's current positions and normals ([3V] floats each; either may be NULL),
+ * with the streams drained: what the last update left on the device.  MPT_ERR_NO_SCENE without a
+ * scene, MPT_ERR_INVALID_ARGUMENT for a vertex count other than the scene's. */
+int mpt_get_vertices(MptContext* ctx, float* out_vertices_or_NULL, float* out_normals_or_NULL, int32_t num_vertices);
 /* Animation clips (DESIGN.md §2 "Geometry updates", Animation): one glTF clip sampled, the node
  * hierarchy composed and the joint palette and morph weights produced ON THE DEVICE, straight into
  * the staging buffers the skin and morph kernels read: a frame of playback is one float.
