@@ -24,6 +24,7 @@
 #include "mpt.h"
 #include "mpt_internal.h"
 #include "refit.h"
+#include "temporal.h"
 #include "upload.h"
 
 using namespace mpt;
@@ -384,6 +385,17 @@ struct MptContext {
     DBuf<int32_t> nrm_group, nrm_row, nrm_tri;
     DBuf<uint8_t> nrm_flip;
     DBuf<float4> nrm_face;
+    // temporal accumulation (mpt_set_temporal, temporal.hip): the pose at the last temporal call
+    // (prev_pos, written by the head hook of the first geometry update after it: tmp_dirty), the
+    // history's two ping-pong plane pairs (tmp_cur: the pair the last call wrote; tmp_valid: it
+    // holds a frame of tmp_w x tmp_h), the last call's visibility, motion and output planes and
+    // the camera it was given
+    bool temporal = false, tmp_dirty = false, tmp_valid = false;
+    bool tmp_stats = false;               // MPT_TEMPORAL_STATS at mpt_create: per-launch times of every call, printed
+    int tmp_cur = 0, tmp_w = 0, tmp_h = 0;
+    DBuf<float> prev_pos, tmp_out;
+    DBuf<float4> tmp_ha[2], tmp_hb[2], tmp_vis, tmp_motion;
+    MptCamera tmp_prev_cam{};
 };
 
 namespace {
@@ -1158,6 +1170,7 @@ int mpt_create(int device, void* hip_stream, MptContext** out) {
     if (const char* e = std::getenv("MPT_SHADE_SPLIT")) c->shade_split = std::atoi(e);
     if (const char* e = std::getenv("MPT_SHADE_TEXMETAL")) c->shade_texmetal = std::atoi(e);
     if (const char* e = std::getenv("MPT_LIGHT_BVH")) c->light_bvh = std::atoi(e);
+    c->tmp_stats = std::getenv("MPT_TEMPORAL_STATS") != nullptr;
     if (const char* e = std::getenv("MPT_OVERLAP")) c->overlap = std::atoi(e);
     if (const char* e = std::getenv("MPT_LIGHT_BVH_MAX_STACK")) c->light_bvh_max_stack = std::atoi(e);
     if (const char* e = std::getenv("MPT_REFIT_HOST")) c->refit_host_loop = std::atoi(e);
@@ -1257,6 +1270,19 @@ static void drop_normals(MptContext* c) {
     release_all(c->nrm_group, c->nrm_row, c->nrm_tri, c->nrm_flip, c->nrm_face);
 }
 
+// The temporal accumulation's history and planes freed (the switch stays): by mpt_resize and, with
+// the previous pose, by a scene upload and mpt_set_temporal(0).
+static void drop_temporal_history(MptContext* c) {
+    c->tmp_valid = false;
+    c->tmp_cur = 0;
+    c->tmp_w = c->tmp_h = 0;
+    release_all(c->tmp_ha[0], c->tmp_ha[1], c->tmp_hb[0], c->tmp_hb[1], c->tmp_vis, c->tmp_motion, c->tmp_out);
+}
+static void drop_temporal_pose(MptContext* c) {
+    c->tmp_dirty = false;
+    c->prev_pos.release();
+}
+
 // The object table of mpt_set_objects, or the skin of mpt_set_skin and the morph of mpt_set_morph
 // (a table excludes the other two), the rest pose and the staging arrays freed.
 static void drop_objects(MptContext* c) {
@@ -1279,6 +1305,7 @@ static void take_scene_mirrors(MptContext* c, const MptScene* s) {
     c->tris_light.release();
     drop_objects(c);          // a new scene: the objects or the skin and the rest pose were the old one's
     drop_normals(c);          // (its table was made over the old scene's indices)
+    if (c->temporal) { drop_temporal_history(c); drop_temporal_pose(c); }   // (another scene's primitives and vertices)
     c->vert_used.release();
 }
 
@@ -1387,6 +1414,23 @@ int mpt_update_materials(MptContext* c, const MptMaterial* m, int32_t count) {
 }
 
 namespace {
+
+// The head hook of every geometry update, before it touches pos (mpt_set_temporal): the first
+// update since the last temporal call copies pos to prev_pos on the stream; later ones leave the
+// older pose there.  Off: one branch.
+hipError_t temporal_snapshot(MptContext* c) {
+    if (!c->temporal || c->tmp_dirty) return hipSuccess;
+    hipError_t e = c->prev_pos.alloc(c->pos.n);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->prev_pos.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) c->tmp_dirty = true;
+    else { (void)hipGetLastError(); c->prev_pos.release(); }
+    return e;
+}
+#define TEMPORAL_HOOK(c)                                                                     \
+    do {                                                                                     \
+        hipError_t e_ = temporal_snapshot(c);                                                \
+        if (e_ != hipSuccess) return alloc_fail(e_, "temporal: previous pose");              \
+    } while (0)
 
 // The upload step of mpt_update_vertices: the streams drained, the host arrays copied over the
 // context's.  Any HIP error is returned; the caller then drops the scene.
@@ -1583,6 +1627,7 @@ int update_pose(MptContext* c, const float* weights, const float* matrices, MptR
         std::memcpy(wpad.data(), weights, (size_t)c->num_targets * sizeof(float));
     }
     HIPCHK(hipSetDevice(c->device));
+    TEMPORAL_HOOK(c);
     hipStream_t st = c->stream;
     float m = 0.0f;
     bool bad = false;
@@ -1655,6 +1700,7 @@ int mpt_update_vertices(MptContext* c, const float* vertices, const float* verte
     }
     const float pad = std::ldexp(std::max(m, 1.0f), -20);
     HIPCHK(hipSetDevice(c->device));
+    TEMPORAL_HOOK(c);
     c->box_pad = pad;
     hipError_t e = upload_vertices(c, vertices, vertex_normals);
     if (e == hipSuccess) e = refit_and_tables(c, pad, vertices);
@@ -1712,6 +1758,7 @@ int mpt_update_transforms(MptContext* c, const float* matrices, int32_t num_obje
     std::vector<float> recs;
     make_xform_records(matrices, num_objects, recs);
     HIPCHK(hipSetDevice(c->device));
+    TEMPORAL_HOOK(c);
     hipStream_t st = c->stream;
     float m = 0.0f;
     bool bad = false;
@@ -2003,6 +2050,7 @@ int mpt_update_vertices_device(MptContext* c, const float* d_vertices, const flo
             return fail(MPT_ERR_INVALID_ARGUMENT, "not memory of the context's device");
         }
     }
+    TEMPORAL_HOOK(c);
     hipStream_t st = c->stream;
     float m = 0.0f;
     bool bad = false;
@@ -2402,6 +2450,11 @@ int mpt_resize(MptContext* c, int32_t w, int32_t h) {
         release_all(c->den_scratch, c->den_out);
     }
     c->den_samples = 0;
+    if (c->temporal) {   // the history and the previous pose go with every resize
+        HIPCHK(drain(c));
+        drop_temporal_history(c);
+        drop_temporal_pose(c);
+    }
     return ensure_batch(c, 1, false);
 }
 
@@ -3250,6 +3303,193 @@ int mpt_denoise_device(MptContext* c, const MptDenoiseSettings* s, const float* 
     int jr = join_waves(c);
     if (jr != MPT_OK) return jr;
     return denoise_run(c, *s, color, albedo, normals, w, h, dst);
+}
+
+// Temporal accumulation (temporal.hip): k_primary_rays, the raw closest-hit traversal and
+// k_temporal on the context's stream, ordered after the frames enqueued so far like mpt_display.
+int mpt_set_temporal(MptContext* c, int enable) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    if (enable) {
+        c->temporal = true;
+        return MPT_OK;
+    }
+    if (c->temporal) {
+        HIPCHK(drain(c));   // kernels of an earlier call may still read the planes
+        drop_temporal_history(c);
+        drop_temporal_pose(c);
+    }
+    c->temporal = false;
+    return MPT_OK;
+}
+
+int mpt_temporal_reset(MptContext* c) {
+    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->temporal) return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: mpt_set_temporal is off");
+    c->tmp_valid = false;
+    return MPT_OK;
+}
+
+// What refuses a temporal call (MPT_OK: nothing); no state is touched.
+static int temporal_refusal(MptContext* c, const MptTemporalSettings* s, const MptCamera* cam) {
+    if (!c || !s || !cam) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (const char* e = mpttemp::temporal_settings_error(*s)) return fail(MPT_ERR_INVALID_ARGUMENT, e);
+    if (!c->temporal) return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: mpt_set_temporal is off");
+    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->rendered || !c->fb_color.p) return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: no frame rendered");
+    if (c->band_c > 1)
+        return fail(MPT_ERR_UNSUPPORTED, "temporal: a row partition holds only its own rows of the history");
+    if (c->res_x <= 0 || c->n_slots <= 0) return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: no frame rendered");
+    return MPT_OK;
+}
+
+// The accumulation enqueued; on any HIP error the history is dropped.
+static int temporal_run(MptContext* c, const MptTemporalSettings& s, const MptCamera& cam) {
+    const int W = c->res_x, H = c->n_slots / c->res_x;
+    const size_t n = (size_t)c->n_slots;
+    hipStream_t st = c->stream;
+    hipError_t e = hipSuccess;
+    const bool fit = c->tmp_w == W && c->tmp_h == H && c->tmp_out.p;
+    if (!fit || c->raw_o.n != n || c->raw_d.n != n) e = drain(c);   // kernels of an earlier call may still use the planes
+    if (!fit) {
+        drop_temporal_history(c);
+        for (int k = 0; k < 2 && e == hipSuccess; k++) {
+            e = c->tmp_ha[k].alloc(n);
+            if (e == hipSuccess) e = c->tmp_hb[k].alloc(n);
+        }
+        if (e == hipSuccess) e = c->tmp_vis.alloc(n);
+        if (e == hipSuccess) e = c->tmp_motion.alloc(n);
+        if (e == hipSuccess) e = c->tmp_out.alloc(3 * n);
+        if (e == hipSuccess) { c->tmp_w = W; c->tmp_h = H; }
+    }
+    if (e == hipSuccess) e = c->raw_o.alloc(n);
+    if (e == hipSuccess) e = c->raw_d.alloc(n);
+    if (e != hipSuccess) {
+        drop_temporal_history(c);
+        return alloc_fail(e, "temporal: working planes");
+    }
+    const int in = c->tmp_cur, out = in ^ 1;
+    TemporalLaunch a{};
+    a.S = s; a.cur = cam; a.prev = c->tmp_valid ? c->tmp_prev_cam : cam;
+    a.W = W; a.H = H; a.has_history = c->tmp_valid ? 1 : 0;
+    a.hit = c->tmp_vis.p; a.idx = c->idx.p; a.pos = c->pos.p;
+    a.prev_pos = c->tmp_dirty && c->prev_pos.n == c->pos.n ? c->prev_pos.p : c->pos.p;
+    a.color = c->fb_color.p; a.albedo = c->fb_albedo.p; a.normals = c->fb_normal.p;
+    a.hist_in_a = c->tmp_ha[in].p; a.hist_in_b = c->tmp_hb[in].p;
+    a.hist_out_a = c->tmp_ha[out].p; a.hist_out_b = c->tmp_hb[out].p;
+    a.out = c->tmp_out.p; a.motion = c->tmp_motion.p;
+    // MPT_TEMPORAL_STATS (read at mpt_create; tools/temporal_time.py): an event between the launches,
+    // a synchronisation after them and one line with the three GPU times
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    const bool stats = c->tmp_stats;
+    auto mark = [&](int k) {
+        if (stats && e == hipSuccess) e = hipEventCreate(&ev[k]);
+        if (stats && e == hipSuccess) e = hipEventRecord(ev[k], st);
+    };
+    mark(0);
+    if (e == hipSuccess) e = launch_primary_rays(cam, W, H, c->raw_o.p, c->raw_d.p, st);
+    mark(1);
+    if (e == hipSuccess)
+        e = launch_trace_raw(dev_scene(c), c->raw_o.p, c->raw_d.p, (int)n, false, c->tmp_vis.p, nullptr, c->fetch_raw.p, c->spill.p,
+                             c->grid, st);
+    mark(2);
+    if (e == hipSuccess) e = launch_temporal(a, st);
+    mark(3);
+    if (stats) {
+        float ms[3] = {0.0f, 0.0f, 0.0f};
+        if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
+        for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+        if (e == hipSuccess)
+            std::fprintf(stderr, "mpt temporal: rays %.1f trace %.1f temporal %.1f us\n", ms[0] * 1e3f, ms[1] * 1e3f, ms[2] * 1e3f);
+        for (hipEvent_t v : ev)
+            if (v) (void)hipEventDestroy(v);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->tmp_valid = false;
+        return fail(MPT_ERR_HIP, std::string("temporal: ") + hipGetErrorString(e));
+    }
+    c->tmp_cur = out;
+    c->tmp_valid = true;
+    c->tmp_prev_cam = cam;
+    c->tmp_dirty = false;
+    return MPT_OK;
+}
+
+// dst: NULL, a device destination (asynchronous) or a host destination (synchronous) of `bytes` bytes
+static int temporal_copy_out(MptContext* c, const void* src, size_t bytes, void* dst, int dst_is_device) {
+    if (!dst) return MPT_OK;
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && !dst_is_device) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->tmp_valid = false;
+        return fail(MPT_ERR_HIP, std::string("temporal: ") + hipGetErrorString(e));
+    }
+    return MPT_OK;
+}
+
+int mpt_temporal_accumulate(MptContext* c, const MptTemporalSettings* s, const MptCamera* cam, float* dst, int dst_is_device) {
+    int r = temporal_refusal(c, s, cam);
+    if (r != MPT_OK) return r;
+    HIPCHK(hipSetDevice(c->device));
+    r = join_waves(c);
+    if (r != MPT_OK) return r;
+    r = temporal_run(c, *s, *cam);
+    if (r != MPT_OK) return r;
+    return temporal_copy_out(c, c->tmp_out.p, 3 * (size_t)c->n_slots * sizeof(float), dst, dst_is_device);
+}
+
+int mpt_get_temporal(MptContext* c, int kind, void* dst, int dst_is_device) {
+    if (!c || !dst) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->temporal) return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: mpt_set_temporal is off");
+    if (!c->tmp_valid || !c->tmp_out.p) return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: nothing accumulated");
+    // the caller sizes dst from the current partition: the planes of a call made at another frame
+    // size or before a frame of a row partition are kept (the history goes on once a frame of their
+    // size is rendered) but not handed out
+    if (c->band_c > 1 || c->res_x != c->tmp_w || (int64_t)c->n_slots != (int64_t)c->tmp_w * c->tmp_h)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: the planes are of another frame size or partition than the last frame's");
+    const size_t n = (size_t)c->tmp_w * c->tmp_h;
+    const void* src = nullptr;
+    size_t bytes = n * sizeof(float4);
+    switch (kind) {
+    case MPT_TEMPORAL_OUTPUT: src = c->tmp_out.p; bytes = 3 * n * sizeof(float); break;
+    case MPT_TEMPORAL_MOTION: src = c->tmp_motion.p; break;
+    case MPT_TEMPORAL_VISIBILITY: src = c->tmp_vis.p; break;
+    case MPT_TEMPORAL_HISTORY_A: src = c->tmp_ha[c->tmp_cur].p; break;
+    case MPT_TEMPORAL_HISTORY_B: src = c->tmp_hb[c->tmp_cur].p; break;
+    default: return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: bad plane kind");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    if (!dst_is_device) HIPCHK(hipStreamSynchronize(c->stream));
+    return MPT_OK;
+}
+
+int mpt_denoise_temporal(MptContext* c, const MptTemporalSettings* s, const MptCamera* cam, const MptDenoiseSettings* d, float* dst,
+                         int dst_is_device) {
+    if (!d) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
+    int r = temporal_refusal(c, s, cam);
+    if (r != MPT_OK) return r;
+    if (const char* e = mptden::denoise_settings_error(*d)) return fail(MPT_ERR_INVALID_ARGUMENT, e);
+    if (d->sample_number != s->sample_number)
+        return fail(MPT_ERR_INVALID_ARGUMENT, "temporal: the denoiser's sample_number differs from the accumulation's");
+    HIPCHK(hipSetDevice(c->device));
+    r = join_waves(c);
+    if (r != MPT_OK) return r;
+    const size_t n = (size_t)c->n_slots;
+    if (c->den_out.n != 3 * n) {
+        HIPCHK(drain(c));
+        c->den_samples = 0;
+        hipError_t e = c->den_out.alloc(3 * n);
+        if (e != hipSuccess) return alloc_fail(e, "denoise: result buffer");
+    }
+    r = temporal_run(c, *s, *cam);
+    if (r != MPT_OK) return r;
+    r = denoise_run(c, *d, c->tmp_out.p, c->fb_albedo.p, c->fb_normal.p, c->tmp_w, c->tmp_h, c->den_out.p);
+    if (r != MPT_OK) return r;
+    c->den_samples = d->sample_number;
+    return temporal_copy_out(c, c->den_out.p, 3 * n * sizeof(float), dst, dst_is_device);
 }
 
 // ---------------------------------------------------------------------------------------

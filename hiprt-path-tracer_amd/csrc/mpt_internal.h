@@ -585,6 +585,29 @@ hipError_t sah_tree_device(int n, const float* pbox, uint32_t* const ord[2], int
                            SahStats* stats);
 hipError_t launch_trace_raw(const DevScene& S, const float4* o, const float4* d, int n, bool any, float4* out_hit,
                             uint8_t* out_occ, int32_t* fetch_ctr, uint32_t* spill, int grid, hipStream_t st);
+// temporal.hip (temporal.h): the centre rays of a W x H frame in the raw layout of launch_trace_raw
+// ({o, last hit -1}, {d, tmax inf}), and the accumulation itself: every pointer on the device, W * H
+// elements each; hist_in is read only with has_history, hist_in and hist_out are different planes
+hipError_t launch_primary_rays(const MptCamera& cam, int W, int H, float4* o, float4* d, hipStream_t st);
+struct TemporalLaunch {
+    MptTemporalSettings S;
+    MptCamera cur, prev;
+    int W, H, has_history;
+    const float4* hit;                       // {t, u, v, prim bits}
+    const int32_t* idx;
+    const float* pos;
+    const float* prev_pos;
+    const float* color;                      // float3 planes
+    const float* albedo;
+    const float* normals;
+    const float4* hist_in_a;
+    const float4* hist_in_b;
+    float4* hist_out_a;
+    float4* hist_out_b;
+    float* out;                              // float3
+    float4* motion;
+};
+hipError_t launch_temporal(const TemporalLaunch& a, hipStream_t st);
 
 }  // namespace mpt
 

@@ -119,6 +119,7 @@ GPURenderer::GPURenderer(const std::vector<int>& devices) : m_devices(devices) {
     m_render_data.band_count = 1;
     mpt_display_settings_default(&m_display_settings);
     mpt_denoise_settings_default(&m_denoise_settings);
+    mpt_temporal_settings_default(&m_temporal_settings);
 }
 
 GPURenderer::~GPURenderer() {
@@ -457,6 +458,29 @@ void GPURenderer::denoise() {
     DenoiseSettings s = m_denoise_settings;
     s.sample_number = m_render_data.render_settings.sample_number > 1 ? m_render_data.render_settings.sample_number : 1;
     check(mpt_denoise(m_ctxs[0], &s, nullptr, 1));
+}
+
+void GPURenderer::set_temporal(bool on) {
+    for (MptContext* c : m_ctxs) check(mpt_set_temporal(c, on ? 1 : 0));
+}
+
+void GPURenderer::denoise_temporal() {
+    if (m_ctxs.size() != 1) throw std::runtime_error("GPURenderer::denoise_temporal: needs a single context");
+    const int n = m_render_data.render_settings.sample_number > 1 ? m_render_data.render_settings.sample_number : 1;
+    TemporalSettings t = m_temporal_settings;
+    DenoiseSettings s = m_denoise_settings;
+    t.sample_number = n;
+    s.sample_number = n;
+    check(mpt_denoise_temporal(m_ctxs[0], &t, &m_camera, &s, nullptr, 1));
+}
+
+void GPURenderer::temporal_reset() {
+    for (MptContext* c : m_ctxs) check(mpt_temporal_reset(c));
+}
+
+void GPURenderer::get_temporal(int kind, float* dst) {
+    if (m_ctxs.size() != 1) throw std::runtime_error("GPURenderer::get_temporal: needs a single context");
+    check(mpt_get_temporal(m_ctxs[0], kind, dst, 0));
 }
 
 const float* GPURenderer::get_denoised_framebuffer(int* sample_number) {

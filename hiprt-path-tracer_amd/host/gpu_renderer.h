@@ -46,6 +46,7 @@ struct DisplayBuffers {
 using DisplaySettings = MptDisplaySettings;
 // the settings of the a-trous denoiser that stands in OIDN's place (mpt_denoise)
 using DenoiseSettings = MptDenoiseSettings;
+using TemporalSettings = MptTemporalSettings;
 
 // ReSTIR DI across the row bands of several contexts of this process (mpt.h MptHaloExchange):
 // one host thread per context renders its band; at every exchange point each member
@@ -254,6 +255,21 @@ public:
     // display() and write_to_png() show MPT_VIEW_BLEND of the sums and the last denoise()'s result
     // (blend factor: get_display_settings().blend_factor, 1 = the denoised image)
     void set_display_blend_to_denoised();
+    // set_temporal / denoise_temporal (no counterpart in the reference): temporal accumulation for
+    // moving scenes.  set_temporal(true) makes every geometry update above keep the pose before it
+    // on the GPU (mpt_set_temporal).  denoise_temporal takes denoise()'s place after a render that
+    // followed an update: the sums just rendered are blended into the history reprojected with
+    // exact motion vectors -- through skin, morph, animation, transforms and the camera; the
+    // previous camera is the one of the previous call -- and the a-trous filter runs over the
+    // accumulated plane into the kept denoise buffer (mpt_denoise_temporal), on the renderer's
+    // stream, without host synchronisation.  get_temporal downloads a plane of the last call (kind:
+    // MPT_TEMPORAL_*; W * H float3 for the output, float4 else); temporal_reset forgets the
+    // history.  One context only, like denoise().
+    TemporalSettings& get_temporal_settings() { return m_temporal_settings; }
+    void set_temporal(bool on);
+    void denoise_temporal();
+    void temporal_reset();
+    void get_temporal(int kind, float* dst);
 
     MptRenderSettings& get_render_settings() { return m_render_data.render_settings; }
     MptWorldSettings& get_world_settings() { return m_render_data.world_settings; }
@@ -310,6 +326,7 @@ private:
     const float* m_blend_rgb = nullptr;
     bool m_blend_is_device = false;
     DenoiseSettings m_denoise_settings{};
+    TemporalSettings m_temporal_settings{};
     MptStatus m_status{};
     std::vector<MptMaterial> m_original_materials, m_current_materials;
     std::vector<MptFrame> m_pending;        // samples enqueued by the launches of this render()

@@ -24,7 +24,7 @@ from ._build import LIB_PATH
 __all__ = ["abi", "scene", "lib", "GPURenderer", "MptError", "build_envmap", "partition_rows", "display_settings",
            "display_host", "write_png", "denoise_host", "bvh_refit_host", "bvh_build_host", "transform_host", "skin_host",
            "SKIN_LDS_JOINTS", "morph_host", "MORPH_LDS_TARGETS", "animation_tables", "animation_host", "ANIM_LDS_NODES",
-           "normal_groups", "normal_flips", "normals_host"]
+           "normal_groups", "normal_flips", "normals_host", "primary_rays_host", "temporal_host"]
 
 SYMBOLS = [
     "mpt_last_error", "mpt_version", "mpt_abi_sizes", "mpt_create", "mpt_destroy", "mpt_upload_scene",
@@ -44,6 +44,8 @@ SYMBOLS = [
     "mpt_set_morph", "mpt_update_morph", "mpt_update_morph_skin", "mpt_morph_host",
     "mpt_set_animation", "mpt_update_animation", "mpt_animation_host",
     "mpt_set_normals", "mpt_normals_host", "mpt_get_vertices",
+    "mpt_temporal_settings_default", "mpt_set_temporal", "mpt_temporal_accumulate", "mpt_temporal_reset", "mpt_get_temporal",
+    "mpt_denoise_temporal", "mpt_primary_rays_host", "mpt_temporal_host",
 ]
 
 SKIN_LDS_JOINTS = abi.SKIN_LDS_JOINTS
@@ -152,6 +154,15 @@ def lib() -> C.CDLL:
     L.mpt_set_normals.argtypes = [vp, vp, vp, i32, i32]
     L.mpt_normals_host.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp]
     L.mpt_get_vertices.argtypes = [vp, vp, vp, i32]
+    L.mpt_temporal_settings_default.argtypes = [C.POINTER(abi.TemporalSettings)]
+    L.mpt_set_temporal.argtypes = [vp, C.c_int]
+    L.mpt_temporal_accumulate.argtypes = [vp, C.POINTER(abi.TemporalSettings), C.POINTER(abi.Camera), vp, C.c_int]
+    L.mpt_temporal_reset.argtypes = [vp]
+    L.mpt_get_temporal.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.mpt_denoise_temporal.argtypes = [vp, C.POINTER(abi.TemporalSettings), C.POINTER(abi.Camera), C.POINTER(abi.DenoiseSettings),
+                                       vp, C.c_int]
+    L.mpt_primary_rays_host.argtypes = [C.POINTER(abi.Camera), i32, i32, vp]
+    L.mpt_temporal_host.argtypes = [C.POINTER(abi.TemporalHostArgs)]
     _lib = L
     return L
 
@@ -303,6 +314,54 @@ def denoise_host(settings, color, albedo, normals):
     _check(lib().mpt_denoise_host(C.byref(settings), _p(color), _p(albedo), _p(normals), color.shape[1], color.shape[0],
                                   _p(out)))
     return out
+
+
+def primary_rays_host(camera, width, height):
+    """mpt_primary_rays_host, no GPU: the centre rays of a width x height frame as
+    GPURenderer.temporal traces them -> float32 [height * width, 8] in trace_closest's layout."""
+    out = np.zeros((int(width) * int(height), 8), np.float32)
+    _check(lib().mpt_primary_rays_host(C.byref(camera), int(width), int(height), _p(out)))
+    return out
+
+
+def temporal_host(settings, camera, prev_camera, visibility, indices, positions, prev_positions, color, albedo, normals,
+                  history=None):
+    """mpt_temporal_host, no GPU: one temporal accumulation on host arrays -- what GPURenderer.temporal
+    computes.  visibility: float32 [H, W, 4] {t, u, v, prim bits} of the centre rays (the host has no
+    traversal); indices int32 [T, 3]; positions, prev_positions float32 [V, 3]; color (sums over
+    settings.sample_number samples), albedo, normals float32 [H, W, 3]; history: None or the
+    (history_a, history_b) pair of the previous call.  Returns (output [H, W, 3], motion [H, W, 4],
+    history_a [H, W, 4], history_b [H, W, 4])."""
+    vis = np.ascontiguousarray(visibility, np.float32)
+    if vis.ndim != 3 or vis.shape[2] != 4:
+        raise ValueError(f"temporal_host: visibility of shape {vis.shape}")
+    h, w = vis.shape[:2]
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    prev = np.ascontiguousarray(prev_positions, np.float32).reshape(-1, 3)
+    if prev.shape != pos.shape:
+        raise ValueError(f"temporal_host: {prev.shape[0]} previous positions for {pos.shape[0]}")
+    color, albedo, normals = (np.ascontiguousarray(a, np.float32) for a in (color, albedo, normals))
+    for a in (color, albedo, normals):
+        if a.shape != (h, w, 3):
+            raise ValueError(f"temporal_host: plane of shape {a.shape} for a {w} x {h} frame")
+    ha = hb = None
+    if history is not None:
+        ha, hb = (np.ascontiguousarray(a, np.float32) for a in history)
+        if ha.shape != (h, w, 4) or hb.shape != (h, w, 4):
+            raise ValueError(f"temporal_host: history planes of shapes {ha.shape}, {hb.shape}")
+    out, motion = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 4), np.float32)
+    oa, ob = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+    a = abi.TemporalHostArgs()
+    a.settings, a.camera, a.prev_camera = settings, camera, prev_camera
+    a.width, a.height, a.num_vertices, a.num_triangles = w, h, len(pos), len(idx)
+    a.visibility, a.indices, a.positions, a.prev_positions = vis.ctypes.data, idx.ctypes.data, pos.ctypes.data, prev.ctypes.data
+    a.color, a.albedo, a.normals = color.ctypes.data, albedo.ctypes.data, normals.ctypes.data
+    a.history_in_a = None if ha is None else ha.ctypes.data
+    a.history_in_b = None if hb is None else hb.ctypes.data
+    a.history_out_a, a.history_out_b, a.output, a.motion = oa.ctypes.data, ob.ctypes.data, out.ctypes.data, motion.ctypes.data
+    _check(lib().mpt_temporal_host(C.byref(a)))
+    return out, motion, oa, ob
 
 
 def _bvh_arrays(call):
@@ -1066,6 +1125,79 @@ class GPURenderer:
         s.sample_number_2 = n
         s.blend_factor = blend
         return self.display(settings=s, second=ptr)
+
+    # --- temporal accumulation (mpt_set_temporal, csrc/temporal.hip) ------------------------
+    def set_temporal(self, on=True):
+        """mpt_set_temporal: on, every geometry update first keeps the pose before it (the pose at
+        the last temporal call) on the device, so that temporal() can follow each pixel's surface
+        point back through skin, morph, animation, transforms and new vertices.  Off frees the
+        previous pose and the history."""
+        _check(lib().mpt_set_temporal(self.h, int(bool(on))))
+
+    def temporal_settings(self, base=None):
+        """abi.TemporalSettings (the defaults, or a copy of `base`) with sample_number = the samples
+        rendered so far, as denoise_settings() counts."""
+        if self.frame is None:
+            raise MptError(abi.ERR_INVALID_ARGUMENT, "temporal: no frame rendered")
+        s = abi.TemporalSettings.default()
+        if base is not None:
+            C.memmove(C.byref(s), C.byref(base), C.sizeof(s))
+        s.sample_number = self.frame.render_settings.sample_number + 1
+        return s
+
+    def _temporal_args(self, settings, camera):
+        if self.frame is None:
+            raise MptError(abi.ERR_INVALID_ARGUMENT, "temporal: no frame rendered")
+        s = settings if settings is not None else self.temporal_settings()
+        cam = camera if camera is not None else self.frame.current_camera
+        return s, cam
+
+    def temporal(self, settings=None, camera=None):
+        """mpt_temporal_accumulate to the host: the colour sums just rendered blended into the
+        reprojected history -> float32 [rows, W, 3], sums in the units of the framebuffer.
+        settings=None: temporal_settings(); camera=None: the last frame's current_camera.  The
+        previous camera is the one of the previous call."""
+        s, cam = self._temporal_args(settings, camera)
+        out = np.zeros((self.rows(), self.frame.res_x, 3), np.float32)
+        _check(lib().mpt_temporal_accumulate(self.h, C.byref(s), C.byref(cam), _p(out), 0))
+        return out
+
+    def temporal_to_device(self, dev_ptr: int | None = None, settings=None, camera=None):
+        """mpt_temporal_accumulate on the context's stream, no host synchronisation; dev_ptr (rows *
+        W float3 of device memory) also receives the result, None keeps it in the context only."""
+        s, cam = self._temporal_args(settings, camera)
+        _check(lib().mpt_temporal_accumulate(self.h, C.byref(s), C.byref(cam), C.c_void_p(int(dev_ptr)) if dev_ptr else None, 1))
+
+    def temporal_reset(self):
+        """mpt_temporal_reset: the next temporal() starts without history."""
+        _check(lib().mpt_temporal_reset(self.h))
+
+    def temporal_planes(self, kind):
+        """mpt_get_temporal: a plane of the last temporal() -> float32 [rows, W, 3]
+        (abi.TEMPORAL_OUTPUT) or [rows, W, 4] (TEMPORAL_MOTION, _VISIBILITY, _HISTORY_A, _HISTORY_B;
+        the primitive ids are int32 bits in lane 3)."""
+        if self.frame is None:
+            raise MptError(abi.ERR_INVALID_ARGUMENT, "temporal: no frame rendered")
+        out = np.zeros((self.rows(), self.frame.res_x, 3 if kind == abi.TEMPORAL_OUTPUT else 4), np.float32)
+        _check(lib().mpt_get_temporal(self.h, int(kind), _p(out), 0))
+        return out
+
+    def temporal_planes_to_device(self, kind, dev_ptr: int):
+        _check(lib().mpt_get_temporal(self.h, int(kind), C.c_void_p(int(dev_ptr)), 1))
+
+    def denoise_temporal(self, settings=None, camera=None, denoise_settings=None, dev_ptr: int | None = None, to_host=True):
+        """mpt_denoise_temporal: temporal(), then the a-trous filter over the accumulated plane into
+        the kept denoise buffer (denoised(), display_denoised()).  to_host: returns float32 [rows, W,
+        3]; else asynchronous, the result also copied to dev_ptr when given."""
+        s, cam = self._temporal_args(settings, camera)
+        d = denoise_settings if denoise_settings is not None else self.denoise_settings()
+        if to_host:
+            out = np.zeros((self.rows(), self.frame.res_x, 3), np.float32)
+            _check(lib().mpt_denoise_temporal(self.h, C.byref(s), C.byref(cam), C.byref(d), _p(out), 0))
+            return out
+        _check(lib().mpt_denoise_temporal(self.h, C.byref(s), C.byref(cam), C.byref(d),
+                                          C.c_void_p(int(dev_ptr)) if dev_ptr else None, 1))
+        return None
 
     # --- one process per GPU (RCCL, mpt_comm_*) ----------------------------------------
     def comm_init(self, nranks: int, rank: int, uid: bytes):

@@ -19,7 +19,7 @@ INCLUDE = ROOT.parent / "include"
 LIB_PATH = PKG_DIR / "libmpt.so"
 OBJ_DIR = CSRC / "build"
 
-SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp", "display.hip", "denoise.hip", "refit.hip", "lbvh.hip", "ploc.hip", "sah.hip", "upload.hip", "xform.hip", "skin.hip", "morph.hip", "anim.hip", "normals.hip"]
+SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp", "display.hip", "denoise.hip", "refit.hip", "lbvh.hip", "ploc.hip", "sah.hip", "upload.hip", "xform.hip", "skin.hip", "morph.hip", "anim.hip", "normals.hip", "temporal.hip"]
 # mpt_part.hip is compiled once per part (-DMPT_TU_PART=k): the shading and ReSTIR DI kernel
 # instantiations, so that they compile in parallel with the rest
 PARTS = [1, 2, 3, 4, 5, 6, 7]
@@ -111,6 +111,9 @@ ANIM_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "
 # GPURenderer::set_normals / get_vertices over several contexts (tests/test_normals_host_cpp.py)
 NORMALS_TEST = HOST_DIR / "normals_move"
 NORMALS_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "normals_move.cpp"]
+# GPURenderer::set_temporal / denoise_temporal (tests/test_temporal_host_cpp.py)
+TEMPORAL_TEST = HOST_DIR / "temporal_move"
+TEMPORAL_SOURCES = [HOST_DIR / "gpu_renderer.cpp", ROOT.parent / "tests" / "cpp" / "temporal_move.cpp"]
 
 
 def _build_driver(exe: Path, sources, lib: Path, verbose: bool) -> Path:
@@ -135,7 +138,7 @@ def build_host_test(verbose: bool = True) -> Path:
     tests/test_host_cpp.py, tests/test_display_host_cpp.py, tests/test_denoise_host_cpp.py and
     tests/test_refit_host_cpp.py, tests/test_rebuild_host_cpp.py, tests/test_ploc_host_cpp.py,
     tests/test_upload_host_cpp.py, tests/test_xform_host_cpp.py, tests/test_skin_host_cpp.py,
-    tests/test_morph_host_cpp.py, tests/test_anim_host_cpp.py, tests/test_normals_host_cpp.py (plain g++: the host side is
+    tests/test_morph_host_cpp.py, tests/test_anim_host_cpp.py, tests/test_normals_host_cpp.py, tests/test_temporal_host_cpp.py (plain g++: the host side is
     ordinary C++ over the C ABI)."""
     lib = build(verbose=verbose)
     _build_driver(DENOISE_TEST, DENOISE_SOURCES, lib, verbose)
@@ -149,6 +152,7 @@ def build_host_test(verbose: bool = True) -> Path:
     _build_driver(MORPH_TEST, MORPH_SOURCES, lib, verbose)
     _build_driver(ANIM_TEST, ANIM_SOURCES, lib, verbose)
     _build_driver(NORMALS_TEST, NORMALS_SOURCES, lib, verbose)
+    _build_driver(TEMPORAL_TEST, TEMPORAL_SOURCES, lib, verbose)
     return _build_driver(HOST_TEST, HOST_SOURCES, lib, verbose)
 
 

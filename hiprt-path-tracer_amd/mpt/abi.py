@@ -454,6 +454,32 @@ class DenoiseSettings(C.Structure):
 DENOISE_MAX_ITERATIONS = 8
 
 
+class TemporalSettings(C.Structure):
+    """MptTemporalSettings: the temporal accumulation's settings (mpt.h)."""
+    _fields_ = [("sample_number", i32), ("max_history", i32), ("alpha", f32), ("depth_tolerance", f32),
+                ("normal_threshold", f32), ("use_albedo", i32)]
+
+    @classmethod
+    def default(cls):
+        """mpt_temporal_settings_default."""
+        return cls(1, 32, 0.1, 0.02, 0.9, 1)
+
+
+TEMPORAL_MAX_HISTORY = 1024
+# MPT_TEMPORAL_*: the planes of mpt_get_temporal
+TEMPORAL_OUTPUT, TEMPORAL_MOTION, TEMPORAL_VISIBILITY, TEMPORAL_HISTORY_A, TEMPORAL_HISTORY_B = range(5)
+
+
+class TemporalHostArgs(C.Structure):
+    """MptTemporalHostArgs: the arguments of mpt_temporal_host (mpt.h)."""
+    _fields_ = [("settings", TemporalSettings), ("camera", Camera), ("prev_camera", Camera),
+                ("width", i32), ("height", i32), ("num_vertices", i32), ("num_triangles", i32),
+                ("visibility", C.c_void_p), ("indices", C.c_void_p), ("positions", C.c_void_p), ("prev_positions", C.c_void_p),
+                ("color", C.c_void_p), ("albedo", C.c_void_p), ("normals", C.c_void_p),
+                ("history_in_a", C.c_void_p), ("history_in_b", C.c_void_p),
+                ("history_out_a", C.c_void_p), ("history_out_b", C.c_void_p), ("output", C.c_void_p), ("motion", C.c_void_p)]
+
+
 class RefitInfo(C.Structure):
     """MptRefitInfo: what mpt_update_vertices reports (mpt.h)."""
     _fields_ = [("nodes", i32), ("levels", i32), ("light_nodes", i32), ("light_levels", i32),

@@ -1287,6 +1287,107 @@ int mpt_denoise_device(MptContext* ctx, const MptDenoiseSettings* settings, cons
 int mpt_denoise_host(const MptDenoiseSettings* settings, const float* color, const float* albedo, const float* normals,
                      int32_t width, int32_t height, float* dst);
 
+/* ------------------------------------------------------------------------- */
+/* Temporal accumulation: motion-vector history for moving scenes              */
+/* ------------------------------------------------------------------------- */
+/* Every geometry update restarts the sample accumulation, so a playing animation shows a few
+ * samples per pose.  With mpt_set_temporal on, the context keeps the pose before the updates since
+ * the last temporal call (prev_pos, 12 B per vertex) and mpt_temporal_accumulate blends the frame
+ * just rendered into a reprojected history: the closest hit of each pixel's centre ray gives a
+ * primitive and barycentrics, the same combination of the triangle's previous vertices the point
+ * the surface came from, the previous call's camera where it was seen.  Exact for skinned,
+ * morphed, animated and transformed geometry and for a moving camera; the definition is DESIGN.md
+ * §2, the arithmetic csrc/temporal.h, shared by the kernels and the host path bit for bit.  The
+ * visibility query does not alpha-test; reflections and refractions move with the surface they
+ * are seen on. */
+#define MPT_TEMPORAL_MAX_HISTORY 1024
+typedef struct MptTemporalSettings {
+    int32_t sample_number;    /* samples in the colour sums, >= 1 (as MptDenoiseSettings) */
+    int32_t max_history;      /* cap of the history length, 1..MPT_TEMPORAL_MAX_HISTORY */
+    float   alpha;            /* floor of the current frame's blend weight, (0, 1] */
+    float   depth_tolerance;  /* relative, finite, > 0 */
+    float   normal_threshold; /* least cosine between the current and a tap's normal, [-1, 1] */
+    int32_t use_albedo;       /* demodulate exactly as the denoiser does */
+} MptTemporalSettings;
+
+/* The planes of mpt_get_temporal: the accumulated colour (float3, sums over sample_number samples
+ * like MPT_FB_COLOR), and four float4 planes: motion {fx, fy, expected depth, prim bits} -- the
+ * previous call's pixel coordinates of the pixel's surface point ((-1, -1): behind the previous
+ * camera), its distance from the previous camera (-1: a miss) --, visibility {t, u, v, prim bits}
+ * (prim -1: a miss), and the history's two planes {e.r, e.g, e.b, depth} (the demodulated mean,
+ * the distance from the camera or -1) and {n.x, n.y, n.z, length}. */
+#define MPT_TEMPORAL_OUTPUT 0
+#define MPT_TEMPORAL_MOTION 1
+#define MPT_TEMPORAL_VISIBILITY 2
+#define MPT_TEMPORAL_HISTORY_A 3
+#define MPT_TEMPORAL_HISTORY_B 4
+
+/* One sample, max_history 32, alpha 0.1, depth_tolerance 0.02, normal_threshold 0.9, albedo on:
+ * the values the quality test of tests/test_temporal_host.py was run with.  Host only. */
+int mpt_temporal_settings_default(MptTemporalSettings* out);
+/* enable != 0: from now on every geometry update (mpt_update_vertices, _vertices_device,
+ * _transforms, _skin, _morph, _morph_skin, _animation) first copies the positions to prev_pos on
+ * the stream unless an update since the last temporal call has done so already -- two updates
+ * between two temporal calls leave the older pose.  mpt_rebuild_bvh* keeps the previous pose and
+ * the history (the primitive ids are the scene's); mpt_upload_scene* and mpt_resize drop both.
+ * enable == 0 frees everything; a context that never enabled it pays one branch per update. */
+int mpt_set_temporal(MptContext* ctx, int enable);
+/* Accumulates the context's colour sums: k_primary_rays, the raw closest-hit traversal and
+ * k_temporal on the context's stream, after the frames enqueued so far.  camera: the camera the
+ * sums were rendered with; the previous camera is the one given to the previous call (the first
+ * call after a reset: this one).  The result stays in the context (mpt_get_temporal) and is also
+ * copied to dst_rgb_or_NULL (rows * res_x float3): a device destination is asynchronous, a host
+ * destination makes the call synchronous.  The working planes (108 B per pixel and two ray planes
+ * shared with mpt_trace_*) are allocated at the first call.  MPT_ERR_INVALID_ARGUMENT when
+ * mpt_set_temporal is off, before any frame was rendered, without a scene, or on bad settings;
+ * MPT_ERR_UNSUPPORTED on a row partition (band_count > 1).  A refusal changes nothing; a HIP error
+ * drops the history. */
+int mpt_temporal_accumulate(MptContext* ctx, const MptTemporalSettings* settings, const MptCamera* camera,
+                            float* dst_rgb_or_NULL, int dst_is_device);
+/* Forgets the history (not the previous pose): the next call starts at length 1. */
+int mpt_temporal_reset(MptContext* ctx);
+/* A plane of the last mpt_temporal_accumulate (kind: MPT_TEMPORAL_*), rows * res_x elements of the
+ * current partition, copied on the stream; a host destination synchronises.
+ * MPT_ERR_INVALID_ARGUMENT when there is none, and when a frame of another size or of a row
+ * partition has been rendered since that call: the planes keep the size of the call (the history
+ * goes on once a frame of that size is rendered again) and are not handed out meanwhile.
+ * MPT_TEMPORAL_STATS in the environment at mpt_create (tools/temporal_time.py) makes every
+ * mpt_temporal_accumulate of the context synchronise and print the GPU times of its three launches
+ * to stderr; unset, nothing is timed. */
+int mpt_get_temporal(MptContext* ctx, int kind, void* dst, int dst_is_device);
+/* mpt_temporal_accumulate, then the a-trous filter over the accumulated plane with the context's
+ * albedo and normals into the kept denoise buffer: mpt_denoised_buffer and the BLEND view then
+ * show it.  The two settings must carry the same sample_number. */
+int mpt_denoise_temporal(MptContext* ctx, const MptTemporalSettings* settings, const MptCamera* camera,
+                         const MptDenoiseSettings* denoise_settings, float* dst_rgb_or_NULL, int dst_is_device);
+/* The centre rays of a width x height frame as the call traces them, width * height * 8 floats in
+ * mpt_trace_closest's layout (origin, 0, direction, tmax inf).  Host only. */
+int mpt_primary_rays_host(const MptCamera* camera, int32_t width, int32_t height, float* out_rays);
+/* The same pixel functions in a host loop, no GPU.  The host has no traversal: visibility is an
+ * input (width * height float4 {t, u, v, prim bits}, e.g. from mpt_trace_closest on the rays
+ * above).  history_in_a NULL: no history.  history planes, visibility and motion: float4; color,
+ * albedo, normals and output: float3. */
+typedef struct MptTemporalHostArgs {
+    MptTemporalSettings settings;
+    MptCamera camera, prev_camera;
+    int32_t width, height;
+    int32_t num_vertices, num_triangles;
+    const float* visibility;
+    const int32_t* indices;
+    const float* positions;
+    const float* prev_positions;
+    const float* color;
+    const float* albedo;
+    const float* normals;
+    const float* history_in_a;
+    const float* history_in_b;
+    float* history_out_a;
+    float* history_out_b;
+    float* output;
+    float* motion;
+} MptTemporalHostArgs;
+int mpt_temporal_host(const MptTemporalHostArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
