@@ -2,7 +2,7 @@
 // of the same arithmetic (morph.h; DESIGN.md §2 "Geometry updates", Morph targets).
 //
 //   k_morph<G, SKIN, LDS>  G vertices per lane, as k_skin<G> (skin.hip); G = 1 is the default, by
-//                the measurement of DESIGN.md §4 (mpt_api.cpp: morph_group).  The rest pose and the
+//                the measurement of DESIGN.md §4 (mpt_geometry.cpp: morph_group).  The rest pose and the
 //                used-vertex mask are read through vert_io.h, the G + 1 row offsets of the lane's
 //                group are one 16-byte load plus a dword (G = 4), and the lane walks the entries
 //                of each of its vertices in turn: target index (4 B), position delta (12 B) and,

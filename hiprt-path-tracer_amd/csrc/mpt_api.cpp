@@ -1,6 +1,7 @@
 // mpt_api.cpp -- the C ABI of libmpt (include/mpt.h).  Owns all device memory of a
 // context (one per GPU), builds the BVH8 on scene upload, stages per-frame settings
-// and launches the wavefront frame (mpt_kernels.hip).
+// and launches the wavefront frame (mpt_kernels.hip).  The geometry updates are
+// mpt_geometry.cpp's; mpt_context.h is what the two share.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -16,389 +17,20 @@
 #include <string>
 #include <vector>
 
-#include "bvh8.h"
 #include "denoise.h"
 #include "display.h"
-#include "morph.h"
-#include "normals.h"
-#include "mpt.h"
-#include "mpt_internal.h"
+#include "mpt_context.h"
 #include "refit.h"
 #include "temporal.h"
 #include "upload.h"
 
-using namespace mpt;
-
-namespace {
-
-thread_local std::string g_err;
-
+namespace mpt {
+static thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-
-}  // namespace
-
-namespace mpt {
 int api_fail(int code, const char* msg) { return fail(code, msg); }   // for the library's other host files
-}  // namespace mpt
-
-namespace {
-
-#define HIPCHK(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return fail(MPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// Status of a failed allocation / memset: MPT_ERR_OUT_OF_MEMORY for hipErrorOutOfMemory.
-// Clears HIP's last error so that a later launch check does not report it again.
-int alloc_fail(hipError_t e, const std::string& what) {
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, what + ": " + hipGetErrorString(e));
-}
-
-// Device buffer owned by a context (freed by the context's destructor at the latest).
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    DBuf() = default;
-    DBuf(const DBuf&) = delete;
-    DBuf& operator=(const DBuf&) = delete;
-    ~DBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-    hipError_t alloc(size_t count) {
-        if (count == n && p) return hipSuccess;
-        release();
-        if (count == 0) return hipSuccess;
-        hipError_t e = hipMalloc(&p, count * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    hipError_t upload(const T* h, size_t count, hipStream_t s) {
-        hipError_t e = alloc(count);
-        if (e != hipSuccess || count == 0) return e;
-        return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s);
-    }
-};
-
-constexpr int FRAME_RING = 256;   // >= 2 x MPT_MAX_BATCH
-constexpr int PIX_PARTS_MAX = 4;  // row parts of a one-sample frame (MptContext::pix_parts)
-// timing events per frame: one pair per timed launch, 10 per bounce (path, any-hit and two
-// light-hit traversals, split, plain and generic shade, miss, compact, resolve) for up to 65
-// bounces (validate_frame), + camera, ReSTIR, accumulate
-// + the ReSTIR DI kernels (G-buffer, presampling, initial, temporal / spatiotemporal, 4 spatial)
-// samples per batched ReSTIR DI wavefront (<= 50 timed scopes each): a partitioned context's
-// band is 1/N of the frame, so its later bounces need up to 128 samples to reach the
-// single-GPU wavefront size (MPT_RESTIR_MAX_BATCH lowers it, A/B)
-constexpr int RESTIR_MAX_BATCH = 128;
-// x2: the two halves of an overlapped batch
-constexpr int EV_POOL = 2 * 2 * ((10 * 65 + 3 + 8) > 50 * RESTIR_MAX_BATCH ? (10 * 65 + 3 + 8) : 50 * RESTIR_MAX_BATCH);
-constexpr int SPILL_WORDS = 2 * TRAV_SPILL_DEPTH;
-constexpr int MAX_STACK = TRAV_LDS_STACK + TRAV_SPILL_DEPTH;
-
-}  // namespace
-
-struct MptContext {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // overlapped batches (MPT_OVERLAP at mpt_create): the second half of a sample batch runs
-    // on stream2, one pipeline stage behind the first, so that shading waves of one half and
-    // traversal waves of the other share the CUs
-    // MPT_OVERLAP: a path-tracing batch's two halves on two streams: 1 always, 0
-    // never, -1 (default) for wavefronts of at most OVERLAP_AUTO_PATHS paths -- a rank's share of
-    // a split frame at the driver's 20 samples, where the launch tails are a larger part of each
-    // launch (one rank of 2 / 4 / 8: -2.3 / -2.7 / -3.8 %); a whole 1080p frame's 33-41 M paths
-    // keep one stream (+1.2 % only, and its per-kernel times stay unshared)
-    int overlap = -1;
-    hipStream_t stream2 = nullptr;
-    // the third and fourth row parts of a one-sample frame (MptContext::pix_parts): streams,
-    // traversal spill areas, join events
-    hipStream_t streamx[2] = {nullptr, nullptr};
-    hipEvent_t ev_joinx[2] = {nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_first = nullptr, ev_acc = nullptr, ev_join = nullptr;
-    // Overlapped ReSTIR DI batches (MPT_RESTIR_OVERLAP, default on): a batch's per-sample chain
-    // (G-buffer, reuse passes, halo exchanges: many small dependent launches) runs on the
-    // context's stream while the previous batch's shared later-bounce wavefront runs on stream2.
-    // The two batches in flight use the two halves of the path state (restir_half), each with its
-    // own counters; ev_half[h] marks the end of the last wavefront that used half h.
-    int restir_overlap = 1;
-    bool restir_overlap_ok = false;       // prepare_batch found room for both halves
-    int restir_half = 0;
-    hipEvent_t ev_chain = nullptr, ev_half[2] = {nullptr, nullptr}, ev_wave_join = nullptr;
-    bool ev_half_used[2] = {false, false};
-    bool wave_pending = false;            // a wavefront on stream2 not yet joined into the stream
-    // One-sample launch sets as a HIP graph (MPT_GRAPHS, default on): mpt_render_frame's ~50
-    // launches of a path-tracing sample captured once and replayed while the frame differs only in
-    // what the kernels read from it (seeds, sample number, cameras, status flags); the graph reads
-    // its frame from the extra ring slot d_frames[FRAME_RING].  Keyed by those frame fields that
-    // steer the host's launch sequence and by the kernels' by-value arguments (buffer pointers).
-    int graphs = 0;   // MPT_GRAPHS=1: one-sample launch sets replayed from a captured HIP graph (no gain measured, r05e)
-    // one-sample frames of a whole-frame context as row parts on their own streams (MPT_PIX_PARTS:
-    // 0 / 1 off, 2 .. PIX_PARTS_MAX parts)
-    int pix_parts = 3;   // batch-1 C3 6.09 -> 5.44 (2 parts) -> 5.29 ms/spp (3); 4 parts 6.76 (past GPU_MAX_HW_QUEUES), r06d
-    // staged ReSTIR DI stages: the generic-class kernel on a side stream beside the plain one
-    // (MPT_RESTIR_SIDE: 1 for partitions of at most 2^20 pixels, 2 always, 0 never)
-    int restir_side = 1;
-    hipEvent_t ev_side[2] = {nullptr, nullptr};
-    // trace-ahead (MPT_TRACE_AHEAD): the next bounce's path traversal beside this bounce's NEE
-    // traversals and resolve, on streamx[1]
-    int trace_ahead = 1;
-    int ovl_ahead = 1;   // MPT_OVERLAP_AHEAD: trace-ahead in both halves of an overlapped batch
-    hipEvent_t ev_ahead[2] = {nullptr, nullptr};
-    hipEvent_t ev_ahead2[2] = {nullptr, nullptr};   // (the second half of an overlapped batch)
-    uint32_t ahead_launches = 0;   // MptStats::trace_ahead_launches
-    uint32_t pipelined_batches = 0;   // MptStats::pipelined_batches
-    hipGraphExec_t graph_exec = nullptr;
-    std::vector<uint8_t> graph_key;
-    uint32_t graph_launches = 0;
-    uint32_t graph_captures = 0, graph_replays = 0;   // since mpt_enable_stats (MptStats)
-    uint32_t overlapped_batches = 0;
-    int num_cus = 256;
-    int grid = 1024;
-    // scene
-    bool has_scene = false;
-    BVH8 bvh;
-    DBuf<Node8> nodes;
-    DBuf<TriRec> tris;
-    DBuf<float4> tri_attr;               // 5 per triangle (launch_tri_attr)
-    DBuf<float> srgb;                    // 256-entry sRGB decode table (launch_srgb_table)
-    // light-hit BVH (k_trace TM_NEE_LIGHT): the triangles whose emission can be non-black
-    BVH8 bvh_light;
-    DBuf<Node8> nodes_light;
-    DBuf<TriRec> tris_light;
-    std::vector<int32_t> h_light_prims;
-    std::vector<int32_t> h_idx;           // host copies for rebuilding the light BVH on material edits
-    std::vector<float> h_pos;
-    float box_pad = 0.0f;
-    // mpt_update_vertices (refit.hip): the exact node boxes of both trees (6 floats per node) and
-    // the records' padded boxes (scratch); the area sums of the builders' node boxes; whether the
-    // host copies bvh.tris, bvh_light.tris and h_pos still hold the positions before an update
-    // (refresh_mirrors); which vertices the triangles use (the pad is taken over these)
-    DBuf<float> nbox, nbox_light, tbox;
-    double area0 = 0.0, area0_light = 0.0;
-    bool mirrors_stale = false;
-    // mpt_rebuild_bvh (lbvh.hip) swapped in trees built on the device: the host copies' nodes,
-    // records and node boxes follow with the next refresh_mirrors (level_begin and depth at once)
-    bool topology_stale = false;
-    std::vector<uint8_t> h_vert_used;
-    // per-object motion (mpt_set_objects, xform.hip): the object id of every vertex (-1: static),
-    // the rest pose captured when the objects were set, the staging arrays a transform writes
-    // before they are swapped in for pos / nrm, the objects' 21-float records, h_vert_used on the
-    // device (mpt_update_vertices_device reads it as well) and the two reduction words
-    int num_objects = -1;                 // -1: no objects set
-    DBuf<int32_t> vert_obj;
-    DBuf<float> rest_pos, rest_nrm, stage_pos, stage_nrm, xf_recs;
-    DBuf<uint8_t> vert_used;
-    DBuf<uint32_t> xf_red;
-    // skinning (mpt_set_skin, skin.hip): four joint indices and weights per vertex and the joints'
-    // 16-word records.  A skin and an object table exclude each other and share rest_pos /
-    // rest_nrm / stage_pos / stage_nrm: setting one drops the other.
-    int num_joints = -1;                  // -1: no skin set
-    DBuf<int32_t> skin_joints;
-    DBuf<float> skin_weights;
-    DBuf<float4> skin_recs;
-    // morph targets (mpt_set_morph, morph.hip): the per-vertex CSR of morph.h.  A morph composes
-    // with a skin and excludes an object table; morph and skin share the rest pose, captured by
-    // whichever is set first and kept until both are gone.  Retained for the call that brings only
-    // the other half: the last accepted weights (morph_w, padded to a multiple of four floats) and
-    // the last accepted palette (skin_recs; skin_posed false: no skin step).  New weights and
-    // records go to the *_stage buffers and are swapped in when the call is accepted.
-    int num_targets = -1;                 // -1: no morph set
-    DBuf<int32_t> morph_row, morph_tgt;
-    DBuf<float> morph_dpos, morph_dnrm, morph_w, morph_w_stage;
-    bool skin_posed = false;
-    DBuf<float4> skin_recs_stage;
-    // an animation clip (mpt_set_animation, anim.hip): the packed tables with their scratch on the
-    // device (anim: counts and section offsets; its blob is not kept), and the kernel's flag word.
-    // It drives the skin's joints, the morph's targets or both, and goes when either goes.
-    bool has_anim = false;
-    AnimPacked anim;
-    DBuf<unsigned char> anim_blob;
-    DBuf<uint32_t> anim_flag;
-    int refit_host_loop = 0;              // test hook (MPT_REFIT_HOST): the refit by the host loop of refit.h
-    int light_bvh = 1;                    // MPT_LIGHT_BVH at mpt_create: 0 = one closest-hit traversal per light-hit query
-    bool light_bvh_ok = false;            // the light BVH matches the materials (else: the exact closest-hit path)
-    int light_bvh_max_stack = 1 << 30;    // test hook (MPT_LIGHT_BVH_MAX_STACK): a lower traversal-stack limit
-    DBuf<int32_t> idx, mat_idx, mat_prio, emissive, tex_dims;
-    DBuf<float> pos, nrm, uv;
-    DBuf<uint8_t> has_n, tex;
-    DBuf<uint64_t> tex_off;
-    DBuf<MptMaterial> mats;
-    DBuf<MptMaterial> mats_res;   // untextured intersection-time resolution per material
-    DBuf<int32_t> mat_tex;
-    DBuf<float4> em_tab;
-    bool any_tex = false;
-    bool any_glass = false;   // a material of the glass class (MT_GLASS): k_shade<GLASS> is launched
-    double tex_tri_frac = 0.0;            // triangles with a textured material / all (resolve_materials)
-    int mat_private = -1;                 // MPT_MAT_PRIVATE: 1 / 0 force k_shade's MATP, -1 by tex_tri_frac
-    // material-class shading (k_split / k_shade): 1 on (default), 0 off, 2 on with every
-    // plain vertex deferred to the generic kernel (test hook); MPT_SHADE_CLASSES at mpt_create
-    int shade_classes = 1;
-    int restir_staged = 1;                // ReSTIR DI reuse passes staged around their rays (MPT_RESTIR_STAGED)
-    int restir_mono_reuse = 0;            // MPT_RESTIR_MONO_REUSE: the reuse passes monolithic, the initial pass staged
-    int restir_batch = 1;                 // ReSTIR DI samples batched after bounce 0 (MPT_RESTIR_BATCH)
-    int adaptive_batch = 1;               // adaptive samples batched, gated in k_accumulate (MPT_ADAPTIVE_BATCH)
-    int restir_max_batch = RESTIR_MAX_BATCH;   // MPT_RESTIR_MAX_BATCH
-    int shade_glass = 1;                  // glass-class shading kernel (MPT_SHADE_GLASS)
-    int shade_split = 0;                  // plain-class shading stages (MPT_SHADE_SPLIT, LaunchCfg::shade_split)
-    int shade_texmetal = 1;               // MT_TEXMETAL materials through the plain list (MPT_SHADE_TEXMETAL)
-    std::vector<MptMaterial> h_mats;
-    std::vector<int32_t> h_mat_idx;       // per triangle (alpha flags of the triangle records)
-    std::vector<uint8_t> h_tex_alpha;     // per texture: some texel has alpha < 255
-    int n_tex = 0;
-    // luts / envmap
-    DBuf<float> lut_conductor, lut_glossy, lut_glass, lut_glass_inv, lut_thin, lut_sheen;
-    DBuf<float4> env;
-    DBuf<int2> alias;
-    DBuf<float4> env_rich;                // alias entries with their radiance texels (launch_env_rich)
-    DBuf<float> env_cdf;
-    float env_cdf_sum = 0.0f;
-    int env_w = 0, env_h = 0;
-    float env_sum = 0.0f;
-    // paths
-    int res_x = 0, res_y = 0, band_h = 1, band_i = 0, band_c = 1, n_slots = 0;   // n_slots = pixels of the partition
-    int batch_cap = 0;      // samples per pixel the path state is sized for (mpt_render_frames)
-    int batch = 1;          // samples of the launch being set up
-    DBuf<float4> ray_o, ray_d, hit, thr, col, alb, nrmv, nq_o, nq_d, nhit, s_gn;
-    DBuf<uint8_t> hit_inside, hit_cls, occ, qmask;
-    DBuf<uint32_t> rng, spill, spill2, spillx[2];
-    DBuf<uint2> seeds;
-    DBuf<uint4> vsA, vsB;
-    DBuf<int32_t> q0, q1, qh, qm, qf, nq_light, counters, nq_tgt, fetch_raw;
-    DBuf<float4> nthr, na, nb, ndir, nris, ne1, ne2;   // NEE record planes (mpt_internal.h)
-    // bounce pipeline (LaunchCfg::pipe_alt): the odd bounces' NEE planes, staged queries and their
-    // lists, shaded lists, and both parities' col additions (MPT_PIPELINE)
-    DBuf<float4> nthr2, na2, nb2, ndir2, nris2, ne12, ne22, nq_o2, nq_d2, ce, ce2;
-    DBuf<int32_t> nq_tgt2, qh2, qf2;
-    int pipeline = 1;
-    size_t pipe_n = 0;
-    hipEvent_t ev_nee[4] = {nullptr, nullptr, nullptr, nullptr};   // fork / join per NEE stream
-    int pix_pipe = 1;   // MPT_PIX_PIPE: a one-sample frame as 2 row parts, each pipelined
-    DBuf<float> fb_color, fb_albedo, fb_normal;
-    DBuf<int32_t> as_count, as_conv;
-    DBuf<float> as_sqlum;
-    DBuf<uint8_t> active;
-    DBuf<uint32_t> status;
-    // ReSTIR DI (allocated on the first LSS_RESTIR_DI frame)
-    DBuf<float4> gb_pos, gb_sn, gb_gn, gb_view, pgb_pos, pgb_sn, pgb_gn, pgb_view;
-    DBuf<int4> gb_meta, pgb_meta;
-    DBuf<uint4> gb_vsA, gb_vsB, pgb_vsA, pgb_vsB;
-    DBuf<MptMaterial> gb_mat, pgb_mat;
-    DBuf<float4> gb_cs, pgb_cs;           // compact surface records (4 float4 per pixel)
-    DBuf<float4> rs_init, rs_sp1, rs_sp2, rs_plights;
-    DBuf<float4> rs_keep;                 // batched ReSTIR DI: the final reservoirs of each sample of a batch
-    DBuf<int32_t> rs_conv;
-    // staged ReSTIR DI passes (DevPaths::rq_*): RS_RPP ray positions per pixel slot
-    DBuf<float4> rq_o, rq_d, rq_rec;
-    DBuf<uint32_t> rq_key;
-    DBuf<uint8_t> rq_occ;
-    DBuf<int32_t> rq_list, rq_items;
-    DBuf<int4> rq_meta;
-    // chunked ReSTIR DI initial candidates (launch_frames_restir, LaunchCfg::ci_planes): the
-    // G-buffer, initial reservoirs and presampled lights of up to restir_chunk samples
-    int restir_chunk = -1;                // MPT_RESTIR_CHUNK: samples per chunk (-1: by the band's pixels)
-    int ci_chunk = 1;                     // the chunk the planes below are sized for
-    DBuf<float4> ci_pos, ci_sn, ci_gn, ci_view, ci_cs, ci_rs, ci_pl;
-    DBuf<int4> ci_meta;
-    DBuf<uint4> ci_vsA, ci_vsB;
-    DBuf<MptMaterial> ci_mat;
-    DevPaths ci_dp{};
-    int restir_out_sp2 = 0;
-    MptHaloExchangeFn halo_fn = nullptr;   // ReSTIR DI across a row partition
-    void* halo_user = nullptr;
-    int halo_prev = 0;                     // halo agreed in the previous frame
-    int32_t* h_reproj = nullptr;           // pinned readback of the reprojection offset
-    DBuf<MptMaterial> mat_slot;
-    // extended light sampling (ensure_ext): x_per entries per path slot of the current batch
-    DBuf<float4> xq_o, xq_d, xq_hit, xrec;
-    DBuf<uint8_t> xq_occ, xq_flag;
-    DBuf<int32_t> xl_any, xl_cl, xl_light;
-    int x_per = 0, x_iter = 0;
-    DBuf<uint64_t> stats;
-    DBuf<uint64_t> ray_counts;
-    // frames
-    MptFrame* h_frames = nullptr;   // pinned ring
-    MptFrame* d_frames = nullptr;
-    int frame_slot = 0;
-    // stats
-    bool timing = false;
-    bool instrumented = false;
-    // two event pools used by alternate frames: a pool is read back when it is
-    // reused two frames later, so collecting timings never stalls the stream
-    hipEvent_t ev[2][EV_POOL];
-    int ev_mode[2][EV_POOL / 2];
-    hipEvent_t ev_frame[2][2];
-    int ev_used[2] = {0, 0};
-    bool ev_pending[2] = {false, false};
-    uint32_t frames_submitted = 0;
-    uint32_t trace_launches = 0;
-    uint32_t frames = 0;
-    double stage_ms[KT_COUNT] = {};
-    uint32_t stage_launches[KT_COUNT] = {};
-    double frame_ms = 0.0;
-    // raw traces
-    DBuf<float4> raw_o, raw_d, raw_hit;
-    DBuf<uint8_t> raw_occ;
-    // one process per GPU (mpt_comm_*): the RCCL communicator of the frame partition and the
-    // padded staging rows of mpt_comm_gather (send: this rank's rows, recv: every rank's, root)
-    void* comm = nullptr;
-    int comm_rank = 0, comm_size = 1;
-    // the library's own halo exchange (mpt_set_halo_native): 1 RCCL send / receive over the
-    // communicator, 2 the one-GPU rehearsal (the bytes moved locally, no peers)
-    int halo_native = 0;
-    DBuf<uint8_t> halo_scratch;           // rehearsal: where the bytes go
-    DBuf<int32_t> halo_agree;             // device word of the halo agreement (ncclAllReduce max)
-    std::vector<MptHaloOp> halo_plan_ops; // the exchange point's operations (native_halo)
-    uint64_t halo_exchanges = 0, halo_agreements = 0, halo_bytes_sent = 0, halo_bytes_recv = 0;   // MptStats
-    uint32_t restir_overlapped_batches = 0;
-    // upper bound of pixel_sample_count over the partition's pixels (restir_gate_static): a reset
-    // frame restarts it, every frame with the adaptive buffers adds at most one sample; unknown
-    // (large) until a reset frame has been launched
-    int as_bound = 1 << 30;
-    // a converged count may be set since the last reset (note_conv_set): by a stop-noise frame, or
-    // by an adaptive frame whose bound had passed that frame's minimum.  While it is set, as_bound
-    // at most an adaptive frame's minimum no longer means that no pixel has converged
-    // (restir_gate_static); cleared with the converged counts (a reset frame, a new partition)
-    bool as_conv_set = false;
-    // the last batch reset the adaptive buffers in its k_accumulate (which an overlapped next batch
-    // would run beside): the next ReSTIR DI batch does not overlap it
-    bool as_reset_pending = false;
-    DBuf<uint8_t> comm_send, comm_recv;
-    // mpt_display: a frame has been rendered into the current partition's buffers, whether the
-    // last one had the adaptive-sampling buffers (has_adaptive), the staging of a host
-    // destination and of a host second buffer
-    bool rendered = false, last_adaptive = false;
-    DBuf<uint32_t> disp_out;
-    DBuf<float> disp_second;
-    // mpt_denoise / mpt_denoise_device: the working planes (denoise.hip), the kept result, the
-    // sample count it was made at (0: nothing denoised since the last resize)
-    DBuf<float> den_scratch, den_out;
-    int den_samples = 0;
-    // recomputed normals (mpt_set_normals, normals.hip): every vertex's group id, the by-group CSR
-    // of normals.h over the scene's indices, the groups' flip bytes and the face vectors' scratch
-    // array.  Independent of objects, skin, morph and animation; a scene upload drops it.
-    int num_groups = -1;                  // -1: normals are not recomputed
-    DBuf<int32_t> nrm_group, nrm_row, nrm_tri;
-    DBuf<uint8_t> nrm_flip;
-    DBuf<float4> nrm_face;
-    // temporal accumulation (mpt_set_temporal, temporal.hip): the pose at the last temporal call
-    // (prev_pos, written by the head hook of the first geometry update after it: tmp_dirty), the
-    // history's two ping-pong plane pairs (tmp_cur: the pair the last call wrote; tmp_valid: it
-    // holds a frame of tmp_w x tmp_h), the last call's visibility, motion and output planes and
-    // the camera it was given
-    bool temporal = false, tmp_dirty = false, tmp_valid = false;
-    bool tmp_stats = false;               // MPT_TEMPORAL_STATS at mpt_create: per-launch times of every call, printed
-    int tmp_cur = 0, tmp_w = 0, tmp_h = 0;
-    DBuf<float> prev_pos, tmp_out;
-    DBuf<float4> tmp_ha[2], tmp_hb[2], tmp_vis, tmp_motion;
-    MptCamera tmp_prev_cam{};
-};
-
-namespace {
 
 DevScene dev_scene(MptContext* c) {
     DevScene S{};
@@ -442,6 +74,67 @@ DevScene dev_scene(MptContext* c) {
     S.env_cdf = c->env_cdf.p;
     S.env_cdf_sum = c->env_cdf_sum;
     return S;
+}
+
+// Both of the context's streams drained (before buffers an overlapped ReSTIR DI wavefront on
+// stream2 may still read are released or reallocated)
+hipError_t drain(MptContext* c) {
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && c->stream2) e = hipStreamSynchronize(c->stream2);
+    for (hipStream_t x : c->streamx)
+        if (e == hipSuccess && x) e = hipStreamSynchronize(x);
+    return e;
+}
+
+// The host copies of the triangle records and of the positions brought up to the device's, after
+// mpt_update_vertices refitted those on the GPU: before a material edit re-stamps and re-uploads
+// the records, or builds a changed light set (upload_alpha_flags, resolve_materials,
+// build_light_bvh_impl).  An update itself pays no host pass over the triangles.
+int refresh_mirrors(MptContext* c) {
+    if (!c->mirrors_stale) return MPT_OK;
+    hipStream_t st = c->stream;
+    if (c->topology_stale) {   // trees rebuilt on the device: sizes, nodes and exact boxes as well
+        const bool light = has_light_tree(c);
+        c->bvh.nodes.resize(c->nodes.n);
+        c->bvh.tris.resize(c->tris.n);
+        c->bvh.node_box.resize(c->nbox.n);
+        HIPCHK(hipMemcpyAsync(c->bvh.nodes.data(), c->nodes.p, c->nodes.n * sizeof(Node8), hipMemcpyDeviceToHost, st));
+        if (c->nbox.n == 6 * c->nodes.n)
+            HIPCHK(hipMemcpyAsync(c->bvh.node_box.data(), c->nbox.p, c->nbox.n * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (light) {
+            c->bvh_light.nodes.resize(c->nodes_light.n);
+            c->bvh_light.tris.resize(c->tris_light.n);
+            c->bvh_light.node_box.resize(c->nbox_light.n);
+            HIPCHK(hipMemcpyAsync(c->bvh_light.nodes.data(), c->nodes_light.p, c->nodes_light.n * sizeof(Node8), hipMemcpyDeviceToHost, st));
+            if (c->nbox_light.n == 6 * c->nodes_light.n)
+                HIPCHK(hipMemcpyAsync(c->bvh_light.node_box.data(), c->nbox_light.p, c->nbox_light.n * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        c->topology_stale = false;
+    }
+    if (c->tris.n != c->bvh.tris.size() || c->pos.n != c->h_pos.size()) return fail(MPT_ERR_HIP, "refresh_mirrors: sizes differ");
+    HIPCHK(hipMemcpyAsync(c->bvh.tris.data(), c->tris.p, c->tris.n * sizeof(TriRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_pos.data(), c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (c->tris_light.p && c->tris_light.n == c->bvh_light.tris.size())
+        HIPCHK(hipMemcpyAsync(c->bvh_light.tris.data(), c->tris_light.p, c->tris_light.n * sizeof(TriRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->mirrors_stale = false;
+    return MPT_OK;
+}
+
+}  // namespace mpt
+
+namespace {
+
+constexpr int FRAME_RING = 256;   // >= 2 x MPT_MAX_BATCH
+constexpr int PIX_PARTS_MAX = 4;  // row parts of a one-sample frame (MptContext::pix_parts)
+constexpr int SPILL_WORDS = 2 * TRAV_SPILL_DEPTH;
+constexpr int MAX_STACK = TRAV_LDS_STACK + TRAV_SPILL_DEPTH;
+
+// The scene BVH8's traversal-stack limit, as build_scene_bvh8 reads it (MPT_BVH_MAX_STACK lowers it).
+int bvh_stack_cap() {
+    const char* e = std::getenv("MPT_BVH_MAX_STACK");
+    return e ? std::max(4, std::min(MAX_STACK, std::atoi(e))) : MAX_STACK;
 }
 
 DevPaths dev_paths(MptContext* c) {
@@ -524,9 +217,6 @@ int rows_of(int res_y, int bh, int bi, int bc) {
     return r;
 }
 
-template <typename... B>
-void release_all(B&... b) { (b.release(), ...); }
-
 // Allocation chain of one buffer group: stops at the first failure, which the caller
 // reports after releasing the whole group (a half-allocated group is never kept).
 struct Allocs {
@@ -562,16 +252,6 @@ void release_batch(MptContext* c) {
 // partition (+ the per-slot resolved materials when `mat_slot`); grows on demand.  On a
 // failure every path-state buffer is released (batch_cap = 0), so that the next call
 // allocates again instead of launching on a half-allocated state.
-// Both of the context's streams drained (before buffers an overlapped ReSTIR DI wavefront on
-// stream2 may still read are released or reallocated)
-static hipError_t drain(MptContext* c) {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && c->stream2) e = hipStreamSynchronize(c->stream2);
-    for (hipStream_t x : c->streamx)
-        if (e == hipSuccess && x) e = hipStreamSynchronize(x);
-    return e;
-}
-
 int ensure_batch(MptContext* c, int batch, bool mat_slot) {
     const size_t pix = (size_t)std::max(c->n_slots, 1);
     const bool have = batch <= c->batch_cap && c->ray_o.p;
@@ -663,42 +343,6 @@ int ensure_paths(MptContext* c, int rx, int ry, int bh, int bi, int bc) {
         return alloc_fail(A.e, "framebuffers for " + std::to_string(N) + " pixels");
     }
     c->res_x = rx; c->res_y = ry; c->band_h = bh; c->band_i = bi; c->band_c = bc; c->n_slots = n;
-    return MPT_OK;
-}
-
-// The host copies of the triangle records and of the positions brought up to the device's, after
-// mpt_update_vertices refitted those on the GPU: before a material edit re-stamps and re-uploads
-// the records, or builds a changed light set (upload_alpha_flags, resolve_materials,
-// build_light_bvh_impl).  An update itself pays no host pass over the triangles.
-int refresh_mirrors(MptContext* c) {
-    if (!c->mirrors_stale) return MPT_OK;
-    hipStream_t st = c->stream;
-    if (c->topology_stale) {   // trees rebuilt on the device: sizes, nodes and exact boxes as well
-        const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
-        c->bvh.nodes.resize(c->nodes.n);
-        c->bvh.tris.resize(c->tris.n);
-        c->bvh.node_box.resize(c->nbox.n);
-        HIPCHK(hipMemcpyAsync(c->bvh.nodes.data(), c->nodes.p, c->nodes.n * sizeof(Node8), hipMemcpyDeviceToHost, st));
-        if (c->nbox.n == 6 * c->nodes.n)
-            HIPCHK(hipMemcpyAsync(c->bvh.node_box.data(), c->nbox.p, c->nbox.n * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (light) {
-            c->bvh_light.nodes.resize(c->nodes_light.n);
-            c->bvh_light.tris.resize(c->tris_light.n);
-            c->bvh_light.node_box.resize(c->nbox_light.n);
-            HIPCHK(hipMemcpyAsync(c->bvh_light.nodes.data(), c->nodes_light.p, c->nodes_light.n * sizeof(Node8), hipMemcpyDeviceToHost, st));
-            if (c->nbox_light.n == 6 * c->nodes_light.n)
-                HIPCHK(hipMemcpyAsync(c->bvh_light.node_box.data(), c->nbox_light.p, c->nbox_light.n * sizeof(float), hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        c->topology_stale = false;
-    }
-    if (c->tris.n != c->bvh.tris.size() || c->pos.n != c->h_pos.size()) return fail(MPT_ERR_HIP, "refresh_mirrors: sizes differ");
-    HIPCHK(hipMemcpyAsync(c->bvh.tris.data(), c->tris.p, c->tris.n * sizeof(TriRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_pos.data(), c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (c->tris_light.p && c->tris_light.n == c->bvh_light.tris.size())
-        HIPCHK(hipMemcpyAsync(c->bvh_light.tris.data(), c->tris_light.p, c->tris_light.n * sizeof(TriRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    c->mirrors_stale = false;
     return MPT_OK;
 }
 
@@ -1242,56 +886,6 @@ static int check_scene(const MptScene* s) {
     return MPT_OK;
 }
 
-// The animation freed: with the skin or the morph it drives, or by mpt_set_animation(NULL).
-static void drop_animation(MptContext* c) {
-    c->has_anim = false;
-    c->anim = AnimPacked();
-    release_all(c->anim_blob, c->anim_flag);
-}
-
-// The skin's tables and its retained palette freed (the rest pose stays).
-static void drop_skin_tables(MptContext* c) {
-    drop_animation(c);
-    c->num_joints = -1;
-    c->skin_posed = false;
-    release_all(c->skin_joints, c->skin_weights, c->skin_recs, c->skin_recs_stage);
-}
-
-// The morph's tables and its retained weights freed (the rest pose stays).
-static void drop_morph_tables(MptContext* c) {
-    drop_animation(c);
-    c->num_targets = -1;
-    release_all(c->morph_row, c->morph_tgt, c->morph_dpos, c->morph_dnrm, c->morph_w, c->morph_w_stage);
-}
-
-// The state of mpt_set_normals freed: by mpt_set_normals(NULL) or a scene upload.
-static void drop_normals(MptContext* c) {
-    c->num_groups = -1;
-    release_all(c->nrm_group, c->nrm_row, c->nrm_tri, c->nrm_flip, c->nrm_face);
-}
-
-// The temporal accumulation's history and planes freed (the switch stays): by mpt_resize and, with
-// the previous pose, by a scene upload and mpt_set_temporal(0).
-static void drop_temporal_history(MptContext* c) {
-    c->tmp_valid = false;
-    c->tmp_cur = 0;
-    c->tmp_w = c->tmp_h = 0;
-    release_all(c->tmp_ha[0], c->tmp_ha[1], c->tmp_hb[0], c->tmp_hb[1], c->tmp_vis, c->tmp_motion, c->tmp_out);
-}
-static void drop_temporal_pose(MptContext* c) {
-    c->tmp_dirty = false;
-    c->prev_pos.release();
-}
-
-// The object table of mpt_set_objects, or the skin of mpt_set_skin and the morph of mpt_set_morph
-// (a table excludes the other two), the rest pose and the staging arrays freed.
-static void drop_objects(MptContext* c) {
-    c->num_objects = -1;
-    release_all(c->vert_obj, c->rest_pos, c->rest_nrm, c->stage_pos, c->stage_nrm, c->xf_recs);
-    drop_skin_tables(c);
-    drop_morph_tables(c);
-}
-
 // What a scene upload keeps on the host besides its trees: the box pad, the vertices in use, the
 // copies of indices and positions; no light set yet.
 static void take_scene_mirrors(MptContext* c, const MptScene* s) {
@@ -1413,666 +1007,6 @@ int mpt_update_materials(MptContext* c, const MptMaterial* m, int32_t count) {
     return resolve_materials(c);
 }
 
-namespace {
-
-// The head hook of every geometry update, before it touches pos (mpt_set_temporal): the first
-// update since the last temporal call copies pos to prev_pos on the stream; later ones leave the
-// older pose there.  Off: one branch.
-hipError_t temporal_snapshot(MptContext* c) {
-    if (!c->temporal || c->tmp_dirty) return hipSuccess;
-    hipError_t e = c->prev_pos.alloc(c->pos.n);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->prev_pos.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) c->tmp_dirty = true;
-    else { (void)hipGetLastError(); c->prev_pos.release(); }
-    return e;
-}
-#define TEMPORAL_HOOK(c)                                                                     \
-    do {                                                                                     \
-        hipError_t e_ = temporal_snapshot(c);                                                \
-        if (e_ != hipSuccess) return alloc_fail(e_, "temporal: previous pose");              \
-    } while (0)
-
-// The upload step of mpt_update_vertices: the streams drained, the host arrays copied over the
-// context's.  Any HIP error is returned; the caller then drops the scene.
-hipError_t upload_vertices(MptContext* c, const float* v, const float* nrm) {
-    hipStream_t st = c->stream;
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->pos.p, v, c->pos.n * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nrm) e = hipMemcpyAsync(c->nrm.p, nrm, c->nrm.n * sizeof(float), hipMemcpyHostToDevice, st);
-    return e;
-}
-
-// Which of normals.hip's two structures recomputes the normals: the two kernels by default, by the
-// measurement of DESIGN.md §4; MPT_NORMALS_FUSED=1 in the environment at the call, the one kernel
-// (tools/normals_time.py measures both)
-bool normals_fused() {
-    const char* e = std::getenv("MPT_NORMALS_FUSED");
-    return e && std::atoi(e) == 1;
-}
-
-// The tail of every geometry update, once pos / nrm hold the new arrays on the device: the refit
-// of both trees and the tables derived from the positions.  host_v: the same positions on the host
-// for the MPT_REFIT_HOST test hook (NULL: always the kernels -- mpt_update_transforms and
-// mpt_update_vertices_device have no host array).
-hipError_t refit_and_tables(MptContext* c, float pad, const float* host_v) {
-#define UV(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-    hipStream_t st = c->stream;
-    const float* v = host_v;
-    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
-    UV(c->nbox.alloc(6 * c->nodes.n));
-    if (light) UV(c->nbox_light.alloc(6 * c->nodes_light.n));
-    if (c->refit_host_loop && v) {
-        // (the host copies' w lanes are always current; their positions are rewritten here; after
-        // a rebuild on the device the copies first take the new trees)
-        if (c->topology_stale && refresh_mirrors(c) != MPT_OK) return hipErrorUnknown;
-        std::vector<float> hb;
-        refit_host(c->bvh, c->h_idx.data(), v, pad, hb);
-        UV(hipMemcpyAsync(c->nodes.p, c->bvh.nodes.data(), c->nodes.n * sizeof(Node8), hipMemcpyHostToDevice, st));
-        UV(hipMemcpyAsync(c->tris.p, c->bvh.tris.data(), c->tris.n * sizeof(TriRec), hipMemcpyHostToDevice, st));
-        UV(hipMemcpyAsync(c->nbox.p, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        UV(hipStreamSynchronize(st));
-        if (light) {
-            refit_host(c->bvh_light, c->h_idx.data(), v, pad, hb);
-            UV(hipMemcpyAsync(c->nodes_light.p, c->bvh_light.nodes.data(), c->nodes_light.n * sizeof(Node8), hipMemcpyHostToDevice, st));
-            UV(hipMemcpyAsync(c->tris_light.p, c->bvh_light.tris.data(), c->tris_light.n * sizeof(TriRec), hipMemcpyHostToDevice, st));
-            UV(hipMemcpyAsync(c->nbox_light.p, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice, st));
-            UV(hipStreamSynchronize(st));
-        }
-        c->h_pos.assign(v, v + c->pos.n);
-        c->mirrors_stale = false;
-    } else {
-        UV(c->tbox.alloc(6 * std::max(c->tris.n, light ? c->tris_light.n : (size_t)0)));
-        c->mirrors_stale = true;
-        UV(launch_refit_tris(c->tris.p, (int)c->tris.n, c->idx.p, c->pos.p, pad, c->tbox.p, st));
-        UV(launch_refit_levels(c->nodes.p, c->nbox.p, c->tbox.p, c->bvh.level_begin.data(), c->bvh.depth, st));
-        if (light) {   // the records hold scene primitive ids: the same path; the scene's pad
-            UV(launch_refit_tris(c->tris_light.p, (int)c->tris_light.n, c->idx.p, c->pos.p, pad, c->tbox.p, st));
-            UV(launch_refit_levels(c->nodes_light.p, c->nbox_light.p, c->tbox.p, c->bvh_light.level_begin.data(),
-                                   c->bvh_light.depth, st));
-        }
-    }
-    // recomputed normals (mpt_set_normals): pos is read, nrm is rewritten in place for the grouped
-    // vertices, on the stream, before the attribute records bake the normals in
-    if (c->num_groups >= 0) {
-        NormalsLaunch a{};
-        a.idx = c->idx.p; a.pos = c->pos.p; a.num_tris = (int)(c->idx.n / 3);
-        a.group = c->nrm_group.p; a.has_n = c->has_n.p; a.row = c->nrm_row.p; a.tri = c->nrm_tri.p; a.flip = c->nrm_flip.p;
-        a.n = (int)c->nrm_group.n; a.nrm = c->nrm.p;
-        const bool fused = normals_fused();
-        if (!fused) UV(c->nrm_face.alloc(std::max(c->idx.n / 3, (size_t)1)));
-        a.face = c->nrm_face.p;
-        UV(launch_normals(a, fused, st));
-    }
-    UV(launch_tri_attr(dev_scene(c), c->tri_attr.p, st));
-    // the emissive-triangle table holds positions (the materials' resolution comes out as it was)
-    UV(launch_resolve_materials(dev_scene(c), c->mats_res.p, c->mat_tex.p, (int)c->h_mats.size(), c->em_tab.p, st));
-    return hipStreamSynchronize(st);
-#undef UV
-}
-
-// The end of every geometry update: e is what the device side returned.  On success the report
-// (a download of the exact node boxes, only when asked for); on a HIP error the scene is dropped.
-int finish_update(MptContext* c, hipError_t e, MptRefitInfo* info, const char* who) {
-    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
-    std::vector<float> hb, hbl;
-    if (e == hipSuccess && info) {
-        hb.resize(c->nbox.n);
-        e = hipMemcpy(hb.data(), c->nbox.p, hb.size() * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && light) {
-            hbl.resize(c->nbox_light.n);
-            e = hipMemcpy(hbl.data(), c->nbox_light.p, hbl.size() * sizeof(float), hipMemcpyDeviceToHost);
-        }
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        c->has_scene = false;   // half updated: the caller uploads again
-        return fail(MPT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    if (info) {
-        MptRefitInfo r{};
-        r.nodes = (int32_t)c->nodes.n;
-        r.levels = c->bvh.depth;
-        r.area_ratio = (float)(node_box_area_sum(hb.data(), c->nodes.n) / c->area0);
-        if (light) {
-            r.light_nodes = (int32_t)c->nodes_light.n;
-            r.light_levels = c->bvh_light.depth;
-            r.light_area_ratio = (float)(node_box_area_sum(hbl.data(), c->nodes_light.n) / c->area0_light);
-        }
-        *info = r;
-    }
-    return MPT_OK;
-}
-
-// h_vert_used on the device (the pad's maximum is taken over the vertices in use).
-hipError_t ensure_used_mask(MptContext* c) {
-    if (c->vert_used.p && c->vert_used.n == c->h_vert_used.size()) return hipSuccess;
-    hipError_t e = c->vert_used.upload(c->h_vert_used.data(), c->h_vert_used.size(), c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) c->vert_used.release();
-    return e;
-}
-
-// The two words a reduction of xform.hip left: the maximum's bits and the non-finite flag; with
-// extra, that device word is read in the same synchronisation and ORed into the flag.
-hipError_t read_reduction(MptContext* c, float* max_abs, bool* bad, const uint32_t* extra = nullptr) {
-    uint32_t w[2] = {0, 0}, x = 0;
-    hipError_t e = hipMemcpyAsync(w, c->xf_red.p, sizeof(w), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && extra) e = hipMemcpyAsync(&x, extra, sizeof(x), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    std::memcpy(max_abs, &w[0], 4);
-    *bad = w[1] != 0 || x != 0;
-    return e;
-}
-
-// vertices per lane of the xform kernels: 4 (MPT_XFORM_GROUP=1 in the environment, read at the
-// call: dword accesses, the same bytes -- tools/xform_time.py measures both)
-int xform_group() {
-    const char* e = std::getenv("MPT_XFORM_GROUP");
-    return e && std::atoi(e) == 1 ? 1 : 4;
-}
-
-// the same for k_skin (MPT_SKIN_GROUP=1), and whether it stages a palette that fits in LDS
-// (MPT_SKIN_LDS=0: always the gather through the cache) -- tools/skin_time.py measures all four
-int skin_group() {
-    const char* e = std::getenv("MPT_SKIN_GROUP");
-    return e && std::atoi(e) == 1 ? 1 : 4;
-}
-bool skin_lds() {
-    const char* e = std::getenv("MPT_SKIN_LDS");
-    return !(e && e[0] == '0' && e[1] == 0);
-}
-// k_morph takes ONE vertex per lane by default: a lane walks its vertices' entries one after the
-// other, and with four vertices that serial walk costs more than the 16-byte accesses save
-// (339 against 1056 us on the dense 4-target city).  MPT_MORPH_GROUP=4 selects four,
-// MPT_MORPH_LDS=0 the gather through the cache -- tools/morph_time.py measures all four
-int morph_group() {
-    const char* e = std::getenv("MPT_MORPH_GROUP");
-    return e && std::atoi(e) == 4 ? 4 : 1;
-}
-bool morph_lds() {
-    const char* e = std::getenv("MPT_MORPH_LDS");
-    return !(e && e[0] == '0' && e[1] == 0);
-}
-// k_anim keeps the world matrices in LDS when they fit (MPT_ANIM_LDS=0: always in memory) --
-// tools/anim_time.py measures both
-bool anim_lds() {
-    const char* e = std::getenv("MPT_ANIM_LDS");
-    return !(e && e[0] == '0' && e[1] == 0);
-}
-
-// The pose of a skin and / or a morph evaluated from the shared rest pose: what mpt_update_skin,
-// mpt_update_morph, mpt_update_morph_skin and mpt_update_animation have in common once their
-// arguments are checked.  weights (NULL: the retained ones) are the morph's num_targets weights,
-// matrices (NULL: the retained palette, if the skin has been posed) the skin's num_joints matrices.
-// anim_time (not NULL: both others NULL): the staged weights and records come from the device
-// instead, written by k_anim for the context's animation -- those of the two that it drives -- and
-// its flag is read with the reductions.  Everything up to the swap writes scratch only -- the new
-// weights and records included -- so a refusal changes nothing, retained state included.
-int update_pose(MptContext* c, const float* weights, const float* matrices, MptRefitInfo* info, const char* who,
-                const float* anim_time = nullptr) {
-    const bool new_w = weights || (anim_time && c->anim.T > 0);
-    const bool new_m = matrices || (anim_time && c->anim.J > 0);
-    const bool morph = c->num_targets >= 0;
-    const bool skin = new_m || (c->num_joints >= 0 && c->skin_posed);
-    const size_t nv = c->pos.n / 3;
-    if (c->rest_pos.n != c->pos.n || c->rest_nrm.n != c->nrm.n) return fail(MPT_ERR_INVALID_ARGUMENT, "rest pose does not fit the scene");
-    if (skin && (3 * c->skin_joints.n != 4 * c->pos.n || c->skin_weights.n != c->skin_joints.n))
-        return fail(MPT_ERR_INVALID_ARGUMENT, "skin does not fit the scene");
-    if (morph && c->morph_row.n != nv + 1) return fail(MPT_ERR_INVALID_ARGUMENT, "morph does not fit the scene");
-    std::vector<float4> recs;
-    if (matrices) make_skin_records(matrices, c->num_joints, recs);
-    std::vector<float> wpad;
-    if (weights) {
-        wpad.assign(((size_t)c->num_targets + 3) / 4 * 4, 0.0f);
-        std::memcpy(wpad.data(), weights, (size_t)c->num_targets * sizeof(float));
-    }
-    HIPCHK(hipSetDevice(c->device));
-    TEMPORAL_HOOK(c);
-    hipStream_t st = c->stream;
-    float m = 0.0f;
-    bool bad = false;
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = ensure_used_mask(c);
-    if (e == hipSuccess) e = c->stage_pos.alloc(c->pos.n);
-    if (e == hipSuccess) e = c->stage_nrm.alloc(c->nrm.n);
-    if (e == hipSuccess) e = c->xf_red.alloc(2);
-    if (e == hipSuccess && matrices) e = c->skin_recs_stage.upload(recs.data(), recs.size(), st);
-    if (e == hipSuccess && weights) e = c->morph_w_stage.upload(wpad.data(), wpad.size(), st);
-    if (anim_time) {
-        // (a buffer the animation does not drive is not touched: k_anim's loop over it is empty)
-        if (e == hipSuccess && new_m) e = c->skin_recs_stage.alloc((size_t)(mptskin::REC / 4) * (size_t)c->anim.J);
-        if (e == hipSuccess && new_w) e = c->morph_w_stage.alloc(((size_t)c->anim.T + 3) / 4 * 4);
-        if (e == hipSuccess)
-            e = launch_anim(anim_tables(c->anim, c->anim_blob.p), *anim_time, c->skin_recs_stage.p, (float4*)c->morph_w_stage.p,
-                            c->anim_flag.p, anim_lds(), st);
-    }
-    const float4* d_recs = new_m ? c->skin_recs_stage.p : c->skin_recs.p;
-    const float* d_w = new_w ? c->morph_w_stage.p : c->morph_w.p;
-    if (e == hipSuccess && !morph)
-        e = launch_skin(c->rest_pos.p, c->rest_nrm.p, c->skin_joints.p, c->skin_weights.p, c->vert_used.p, (const float*)d_recs,
-                        c->num_joints, (int)nv, c->stage_pos.p, c->stage_nrm.p, c->xf_red.p, skin_group(), skin_lds(), st);
-    if (e == hipSuccess && morph) {
-        MorphLaunch a{};
-        a.rest_pos = c->rest_pos.p; a.rest_nrm = c->rest_nrm.p;
-        a.row = c->morph_row.p; a.tgt = c->morph_tgt.p; a.dpos = c->morph_dpos.p; a.dnrm = c->morph_dnrm.p;
-        a.mweights = d_w; a.num_targets = c->num_targets;
-        if (skin) { a.joints = c->skin_joints.p; a.sweights = c->skin_weights.p; a.recs = (const float*)d_recs; a.num_joints = c->num_joints; }
-        a.used = c->vert_used.p; a.n = (int)nv;
-        a.out_pos = c->stage_pos.p; a.out_nrm = c->stage_nrm.p; a.red = c->xf_red.p;
-        e = launch_morph(a, morph_group(), morph_lds(), st);
-    }
-    if (e == hipSuccess) e = read_reduction(c, &m, &bad, anim_time ? c->anim_flag.p : nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        c->has_scene = false;
-        return fail(MPT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, anim_time ? "non-finite animation value or vertex coordinate" : "non-finite vertex coordinate");
-    if (new_m) {
-        std::swap(c->skin_recs.p, c->skin_recs_stage.p); std::swap(c->skin_recs.n, c->skin_recs_stage.n);
-        c->skin_posed = true;
-    }
-    if (new_w) { std::swap(c->morph_w.p, c->morph_w_stage.p); std::swap(c->morph_w.n, c->morph_w_stage.n); }
-    std::swap(c->pos.p, c->stage_pos.p);
-    std::swap(c->nrm.p, c->stage_nrm.p);
-    const float pad = std::ldexp(std::max(m, 1.0f), -20);
-    c->box_pad = pad;
-    return finish_update(c, refit_and_tables(c, pad, nullptr), info, who);
-}
-
-}  // namespace
-
-int mpt_update_vertices(MptContext* c, const float* vertices, const float* vertex_normals, int32_t num_vertices,
-                        MptRefitInfo* info) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!vertices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
-    // one pass: every coordinate finite, and scene_box_pad's maximum over the vertices in use
-    float m = 0.0f;
-    for (size_t i = 0; i < (size_t)num_vertices; i++) {
-        const float* p = vertices + 3 * i;
-        const float a0 = std::fabs(p[0]), a1 = std::fabs(p[1]), a2 = std::fabs(p[2]);
-        if (!(a0 <= FLT_MAX && a1 <= FLT_MAX && a2 <= FLT_MAX))   // (a NaN fails every comparison)
-            return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
-        if (c->h_vert_used[i]) m = std::max(m, std::max(a0, std::max(a1, a2)));
-    }
-    const float pad = std::ldexp(std::max(m, 1.0f), -20);
-    HIPCHK(hipSetDevice(c->device));
-    TEMPORAL_HOOK(c);
-    c->box_pad = pad;
-    hipError_t e = upload_vertices(c, vertices, vertex_normals);
-    if (e == hipSuccess) e = refit_and_tables(c, pad, vertices);
-    return finish_update(c, e, info, "mpt_update_vertices");
-}
-
-int mpt_set_objects(MptContext* c, const int32_t* vertex_object, int32_t num_vertices, int32_t num_objects) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!vertex_object) {
-        if (num_objects != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-        HIPCHK(hipSetDevice(c->device));
-        if (c->num_joints < 0 && c->num_targets < 0) drop_objects(c);   // (a skin or a morph is its own call's to free)
-        return MPT_OK;
-    }
-    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
-    if (num_objects <= 0) return fail(MPT_ERR_INVALID_ARGUMENT, "objects: bad object count");
-    for (int32_t i = 0; i < num_vertices; i++)
-        if (vertex_object[i] < -1 || vertex_object[i] >= num_objects) return fail(MPT_ERR_INVALID_ARGUMENT, "object id out of range");
-    HIPCHK(hipSetDevice(c->device));
-    // into new buffers, swapped in when all of them are there: a failure leaves the old objects
-    DBuf<int32_t> ids;
-    DBuf<float> rp, rn;
-    hipStream_t st = c->stream;
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = ensure_used_mask(c);
-    if (e == hipSuccess) e = ids.upload(vertex_object, (size_t)num_vertices, st);
-    if (e == hipSuccess) e = rp.alloc(c->pos.n);
-    if (e == hipSuccess) e = rn.alloc(c->nrm.n);
-    if (e == hipSuccess) e = hipMemcpyAsync(rp.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(rn.p, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_objects: ") + hipGetErrorString(e));
-    }
-    drop_objects(c);
-    std::swap(c->vert_obj.p, ids.p); std::swap(c->vert_obj.n, ids.n);
-    std::swap(c->rest_pos.p, rp.p); std::swap(c->rest_pos.n, rp.n);
-    std::swap(c->rest_nrm.p, rn.p); std::swap(c->rest_nrm.n, rn.n);
-    c->num_objects = num_objects;
-    return MPT_OK;
-}
-
-int mpt_update_transforms(MptContext* c, const float* matrices, int32_t num_objects, MptRefitInfo* info) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!matrices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (c->num_objects < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no objects set");
-    if (num_objects != c->num_objects) return fail(MPT_ERR_INVALID_ARGUMENT, "object count differs from the table's");
-    if (!matrices_finite(matrices, num_objects)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite matrix entry");
-    if (c->rest_pos.n != c->pos.n || c->rest_nrm.n != c->nrm.n || 3 * c->vert_obj.n != c->pos.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "objects do not fit the scene");
-    std::vector<float> recs;
-    make_xform_records(matrices, num_objects, recs);
-    HIPCHK(hipSetDevice(c->device));
-    TEMPORAL_HOOK(c);
-    hipStream_t st = c->stream;
-    float m = 0.0f;
-    bool bad = false;
-    // everything up to the swap writes scratch only: a refusal or an error here changes nothing
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = ensure_used_mask(c);
-    if (e == hipSuccess) e = c->stage_pos.alloc(c->pos.n);
-    if (e == hipSuccess) e = c->stage_nrm.alloc(c->nrm.n);
-    if (e == hipSuccess) e = c->xf_red.alloc(2);
-    if (e == hipSuccess) e = c->xf_recs.upload(recs.data(), recs.size(), st);
-    if (e == hipSuccess)
-        e = launch_xform(c->rest_pos.p, c->rest_nrm.p, c->vert_obj.p, c->vert_used.p, c->xf_recs.p, (int)c->vert_obj.n,
-                         c->stage_pos.p, c->stage_nrm.p, c->xf_red.p, xform_group(), st);
-    if (e == hipSuccess) e = read_reduction(c, &m, &bad);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        c->has_scene = false;
-        return fail(MPT_ERR_HIP, std::string("mpt_update_transforms: ") + hipGetErrorString(e));
-    }
-    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
-    std::swap(c->pos.p, c->stage_pos.p);
-    std::swap(c->nrm.p, c->stage_nrm.p);
-    const float pad = std::ldexp(std::max(m, 1.0f), -20);
-    c->box_pad = pad;
-    return finish_update(c, refit_and_tables(c, pad, nullptr), info, "mpt_update_transforms");
-}
-
-int mpt_set_skin(MptContext* c, const int32_t* joints, const float* weights, int32_t num_vertices, int32_t num_joints) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!joints && !weights) {
-        if (num_joints != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-        HIPCHK(hipSetDevice(c->device));
-        // (an object table is mpt_set_objects' to free; with a morph set the rest pose stays)
-        if (c->num_targets >= 0) drop_skin_tables(c);
-        else if (c->num_objects < 0) drop_objects(c);
-        return MPT_OK;
-    }
-    if (!joints || !weights) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
-    if (num_joints < 1) return fail(MPT_ERR_INVALID_ARGUMENT, "skin: bad joint count");
-    if (const char* bad = check_skin_table(joints, weights, (size_t)num_vertices, num_joints)) return fail(MPT_ERR_INVALID_ARGUMENT, bad);
-    HIPCHK(hipSetDevice(c->device));
-    // into new buffers, swapped in when all of them are there: a failure leaves what was set
-    DBuf<int32_t> dj;
-    DBuf<float> dw, rp, rn;
-    hipStream_t st = c->stream;
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = ensure_used_mask(c);
-    if (e == hipSuccess) e = dj.upload(joints, 4 * (size_t)num_vertices, st);
-    const bool capture = c->num_targets < 0;   // a morph has captured the rest pose already
-    if (e == hipSuccess) e = dw.upload(weights, 4 * (size_t)num_vertices, st);
-    if (e == hipSuccess && capture) e = rp.alloc(c->pos.n);
-    if (e == hipSuccess && capture) e = rn.alloc(c->nrm.n);
-    if (e == hipSuccess && capture) e = hipMemcpyAsync(rp.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && capture) e = hipMemcpyAsync(rn.p, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_skin: ") + hipGetErrorString(e));
-    }
-    if (capture) {
-        drop_objects(c);
-        std::swap(c->rest_pos.p, rp.p); std::swap(c->rest_pos.n, rp.n);
-        std::swap(c->rest_nrm.p, rn.p); std::swap(c->rest_nrm.n, rn.n);
-    } else {
-        drop_skin_tables(c);      // (the new skin is not posed)
-    }
-    std::swap(c->skin_joints.p, dj.p); std::swap(c->skin_joints.n, dj.n);
-    std::swap(c->skin_weights.p, dw.p); std::swap(c->skin_weights.n, dw.n);
-    c->num_joints = num_joints;
-    return MPT_OK;
-}
-
-int mpt_update_skin(MptContext* c, const float* joint_matrices, int32_t num_joints, MptRefitInfo* info) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!joint_matrices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (c->num_joints < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no skin set");
-    if (num_joints != c->num_joints) return fail(MPT_ERR_INVALID_ARGUMENT, "joint count differs from the table's");
-    if (!matrices_finite(joint_matrices, num_joints)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite matrix entry");
-    return update_pose(c, nullptr, joint_matrices, info, "mpt_update_skin");
-}
-
-int mpt_set_morph(MptContext* c, int32_t num_targets, const int32_t* target_offsets, const int32_t* vertex_ids,
-                  const float* pos_deltas, const float* nrm_deltas, int32_t num_vertices) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!target_offsets && !vertex_ids && !pos_deltas && !nrm_deltas) {
-        if (num_targets != 0) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-        HIPCHK(hipSetDevice(c->device));
-        // (an object table is mpt_set_objects' to free; with a skin set the rest pose stays)
-        if (c->num_joints >= 0) drop_morph_tables(c);
-        else if (c->num_objects < 0) drop_objects(c);
-        return MPT_OK;
-    }
-    if (!target_offsets) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
-    mptmorph::Csr csr;
-    if (const char* bad = mptmorph::to_csr(num_targets, target_offsets, vertex_ids, pos_deltas, nrm_deltas, num_vertices, csr))
-        return fail(MPT_ERR_INVALID_ARGUMENT, bad);
-    HIPCHK(hipSetDevice(c->device));
-    // into new buffers, swapped in when all of them are there: a failure leaves what was set
-    const bool capture = c->num_joints < 0;   // a skin has captured the rest pose already
-    const std::vector<float> zeros(((size_t)num_targets + 3) / 4 * 4, 0.0f);
-    const size_t N = csr.tgt.size();
-    DBuf<int32_t> dr, dt;
-    DBuf<float> dp, dn, dw, rp, rn;
-    hipStream_t st = c->stream;
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = ensure_used_mask(c);
-    if (e == hipSuccess) e = dr.upload(csr.row.data(), csr.row.size(), st);
-    // (a kernel is never handed a NULL table: a morph without entries keeps one unread entry)
-    if (e == hipSuccess) e = dt.alloc(std::max(N, (size_t)1));
-    if (e == hipSuccess) e = dp.alloc(3 * std::max(N, (size_t)1));
-    if (e == hipSuccess && nrm_deltas) e = dn.alloc(3 * std::max(N, (size_t)1));
-    if (e == hipSuccess && N) e = hipMemcpyAsync(dt.p, csr.tgt.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(dp.p, csr.dpos.data(), 3 * N * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && N && nrm_deltas) e = hipMemcpyAsync(dn.p, csr.dnrm.data(), 3 * N * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = dw.upload(zeros.data(), zeros.size(), st);
-    if (e == hipSuccess && capture) e = rp.alloc(c->pos.n);
-    if (e == hipSuccess && capture) e = rn.alloc(c->nrm.n);
-    if (e == hipSuccess && capture) e = hipMemcpyAsync(rp.p, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && capture) e = hipMemcpyAsync(rn.p, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_morph: ") + hipGetErrorString(e));
-    }
-    if (capture) {
-        drop_objects(c);          // an object table, or an earlier morph with its rest pose
-        std::swap(c->rest_pos.p, rp.p); std::swap(c->rest_pos.n, rp.n);
-        std::swap(c->rest_nrm.p, rn.p); std::swap(c->rest_nrm.n, rn.n);
-    } else {
-        drop_morph_tables(c);
-    }
-    std::swap(c->morph_row.p, dr.p); std::swap(c->morph_row.n, dr.n);
-    std::swap(c->morph_tgt.p, dt.p); std::swap(c->morph_tgt.n, dt.n);
-    std::swap(c->morph_dpos.p, dp.p); std::swap(c->morph_dpos.n, dp.n);
-    std::swap(c->morph_dnrm.p, dn.p); std::swap(c->morph_dnrm.n, dn.n);
-    std::swap(c->morph_w.p, dw.p); std::swap(c->morph_w.n, dw.n);
-    c->num_targets = num_targets;
-    return MPT_OK;
-}
-
-int mpt_set_normals(MptContext* c, const int32_t* vertex_group, const uint8_t* group_flip, int32_t num_vertices, int32_t num_groups) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!vertex_group) {
-        if (num_groups != 0 || group_flip) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(drain(c));
-        drop_normals(c);
-        return MPT_OK;
-    }
-    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
-    // (the indices: the context's own copy, taken at the upload -- no update, rebuild or material
-    // edit changes them, so the copy is current also where the other host mirrors are stale)
-    if (3 * (c->h_idx.size() / 3) != c->h_idx.size() || c->h_idx.size() != c->idx.n)
-        return fail(MPT_ERR_HIP, "mpt_set_normals: index mirror differs from the scene's");
-    mptnormals::Csr csr;
-    if (const char* bad = mptnormals::to_csr(vertex_group, num_vertices, num_groups, c->h_idx.data(), (int32_t)(c->h_idx.size() / 3), csr))
-        return fail(MPT_ERR_INVALID_ARGUMENT, bad);
-    const std::vector<uint8_t> zeros(group_flip ? 0 : (size_t)num_groups, 0);
-    HIPCHK(hipSetDevice(c->device));
-    // into new buffers, swapped in when all of them are there: a failure leaves what was set
-    const size_t N = csr.tri.size();
-    DBuf<int32_t> dg, dr, dt;
-    DBuf<uint8_t> df;
-    hipStream_t st = c->stream;
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = dg.upload(vertex_group, (size_t)num_vertices, st);
-    if (e == hipSuccess) e = dr.upload(csr.row.data(), csr.row.size(), st);
-    // (a kernel is never handed a NULL table: groups without entries keep one unread entry)
-    if (e == hipSuccess) e = dt.alloc(std::max(N, (size_t)1));
-    if (e == hipSuccess && N) e = hipMemcpyAsync(dt.p, csr.tri.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = df.upload(group_flip ? group_flip : zeros.data(), (size_t)num_groups, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_normals: ") + hipGetErrorString(e));
-    }
-    drop_normals(c);
-    std::swap(c->nrm_group.p, dg.p); std::swap(c->nrm_group.n, dg.n);
-    std::swap(c->nrm_row.p, dr.p); std::swap(c->nrm_row.n, dr.n);
-    std::swap(c->nrm_tri.p, dt.p); std::swap(c->nrm_tri.n, dt.n);
-    std::swap(c->nrm_flip.p, df.p); std::swap(c->nrm_flip.n, df.n);
-    c->num_groups = num_groups;
-    return MPT_OK;
-}
-
-int mpt_get_vertices(MptContext* c, float* out_vertices, float* out_normals, int32_t num_vertices) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(drain(c));
-    if (out_vertices) HIPCHK(hipMemcpy(out_vertices, c->pos.p, c->pos.n * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_normals) HIPCHK(hipMemcpy(out_normals, c->nrm.p, c->nrm.n * sizeof(float), hipMemcpyDeviceToHost));
-    return MPT_OK;
-}
-
-int mpt_update_morph(MptContext* c, const float* weights, int32_t num_targets, MptRefitInfo* info) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!weights) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (c->num_targets < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no morph set");
-    if (num_targets != c->num_targets) return fail(MPT_ERR_INVALID_ARGUMENT, "target count differs from the tables'");
-    if (!weights_finite(weights, num_targets)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite morph weight");
-    return update_pose(c, weights, nullptr, info, "mpt_update_morph");
-}
-
-int mpt_update_morph_skin(MptContext* c, const float* weights, int32_t num_targets, const float* joint_matrices, int32_t num_joints,
-                          MptRefitInfo* info) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!weights || !joint_matrices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (c->num_targets < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no morph set");
-    if (c->num_joints < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "no skin set");
-    if (num_targets != c->num_targets) return fail(MPT_ERR_INVALID_ARGUMENT, "target count differs from the tables'");
-    if (num_joints != c->num_joints) return fail(MPT_ERR_INVALID_ARGUMENT, "joint count differs from the table's");
-    if (!weights_finite(weights, num_targets)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite morph weight");
-    if (!matrices_finite(joint_matrices, num_joints)) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite matrix entry");
-    return update_pose(c, weights, joint_matrices, info, "mpt_update_morph_skin");
-}
-
-int mpt_set_animation(MptContext* c, const MptAnimation* anim) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!anim) {
-        HIPCHK(hipSetDevice(c->device));
-        drop_animation(c);
-        return MPT_OK;
-    }
-    AnimPacked p;
-    if (const char* bad = pack_animation(*anim, p)) return fail(MPT_ERR_INVALID_ARGUMENT, bad);
-    if (p.J > 0 && c->num_joints < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: joints without a skin set");
-    if (p.J > 0 && p.J != c->num_joints) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: joint count differs from the skin's");
-    if (p.T > 0 && c->num_targets < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: targets without a morph set");
-    if (p.T > 0 && p.T != c->num_targets) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: target count differs from the morph's");
-    HIPCHK(hipSetDevice(c->device));
-    // into new buffers, swapped in when they are there: a failure leaves what was set
-    DBuf<unsigned char> db;
-    DBuf<uint32_t> df;
-    hipStream_t st = c->stream;
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = db.upload(p.blob.data(), p.blob.size(), st);
-    if (e == hipSuccess) e = df.alloc(1);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? MPT_ERR_OUT_OF_MEMORY : MPT_ERR_HIP, std::string("mpt_set_animation: ") + hipGetErrorString(e));
-    }
-    drop_animation(c);
-    std::swap(c->anim_blob.p, db.p); std::swap(c->anim_blob.n, db.n);
-    std::swap(c->anim_flag.p, df.p); std::swap(c->anim_flag.n, df.n);
-    p.blob = std::vector<unsigned char>();   // (only the counts and the offsets are kept)
-    c->anim = std::move(p);
-    c->has_anim = true;
-    return MPT_OK;
-}
-
-int mpt_update_animation(MptContext* c, float time, MptRefitInfo* info) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!c->has_anim) return fail(MPT_ERR_INVALID_ARGUMENT, "no animation set");
-    if (!(std::fabs(time) <= FLT_MAX)) return fail(MPT_ERR_INVALID_ARGUMENT, "animation: time not finite");
-    // (the animation goes with the skin and the morph it drives: the counts still fit)
-    return update_pose(c, nullptr, nullptr, info, "mpt_update_animation", &time);
-}
-
-int mpt_update_vertices_device(MptContext* c, const float* d_vertices, const float* d_normals, int32_t num_vertices,
-                               MptRefitInfo* info) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!d_vertices) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (num_vertices <= 0 || 3 * (size_t)num_vertices != c->pos.n)
-        return fail(MPT_ERR_INVALID_ARGUMENT, "vertex count differs from the scene's");
-    HIPCHK(hipSetDevice(c->device));
-    for (const float* p : {d_vertices, d_normals}) {   // a host pointer must not reach a kernel
-        if (!p) continue;
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
-            (void)hipGetLastError();
-            return fail(MPT_ERR_INVALID_ARGUMENT, "not memory of the context's device");
-        }
-    }
-    TEMPORAL_HOOK(c);
-    hipStream_t st = c->stream;
-    float m = 0.0f;
-    bool bad = false;
-    hipError_t e = drain(c);
-    if (e == hipSuccess) e = ensure_used_mask(c);
-    if (e == hipSuccess) e = c->xf_red.alloc(2);
-    if (e == hipSuccess) e = launch_xform_check(d_vertices, c->vert_used.p, num_vertices, c->xf_red.p, xform_group(), st);
-    if (e == hipSuccess) e = read_reduction(c, &m, &bad);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        c->has_scene = false;
-        return fail(MPT_ERR_HIP, std::string("mpt_update_vertices_device: ") + hipGetErrorString(e));
-    }
-    if (bad) return fail(MPT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate");
-    const float pad = std::ldexp(std::max(m, 1.0f), -20);
-    c->box_pad = pad;
-    e = hipMemcpyAsync(c->pos.p, d_vertices, c->pos.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && d_normals) e = hipMemcpyAsync(c->nrm.p, d_normals, c->nrm.n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = refit_and_tables(c, pad, nullptr);
-    return finish_update(c, e, info, "mpt_update_vertices_device");
-}
-
 // A tree built on the device takes the place of the context's: the buffers change hands, the host
 // copy keeps the levels (its nodes and records follow with refresh_mirrors, topology_stale).
 static void swap_in(DBuf<Node8>& dn, DBuf<TriRec>& dt, DBuf<float>& db, BVH8& h, LbvhDevice& t) {
@@ -2094,10 +1028,9 @@ int mpt_rebuild_bvh_mode(MptContext* c, int32_t mode, MptRebuildInfo* info) {
     if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
+    const bool light = has_light_tree(c);
     const int n_prims = (int)c->mat_idx.n;
-    int stack_cap = MAX_STACK;   // as build_scene_bvh8
-    if (const char* e = std::getenv("MPT_BVH_MAX_STACK")) stack_cap = std::max(4, std::min(MAX_STACK, std::atoi(e)));
+    const int stack_cap = bvh_stack_cap();
     const int light_cap = std::min(MAX_STACK, c->light_bvh_max_stack);
     LbvhDevice T, TL;
     PlocStats ps, psl;
@@ -2130,9 +1063,7 @@ int mpt_rebuild_bvh_mode(MptContext* c, int32_t mode, MptRebuildInfo* info) {
     if (e != hipSuccess) {
         free_lbvh(T);
         free_lbvh(TL);
-        (void)hipGetLastError();
-        c->has_scene = false;   // the caller uploads again
-        return fail(MPT_ERR_HIP, std::string("mpt_rebuild_bvh: ") + hipGetErrorString(e));
+        return update_fail(c, e, "mpt_rebuild_bvh");
     }
     swap_in(c->nodes, c->tris, c->nbox, c->bvh, T);
     c->area0 = node_box_area_sum(hb.data(), (size_t)T.n_nodes);
@@ -2199,8 +1130,7 @@ int mpt_upload_scene_mode(MptContext* c, const MptScene* s, int32_t mode, MptReb
         mf[i] = (material_alpha_flag(c, c->h_mats[i]) ? MF_ALPHA : 0u) | (lit ? MF_LIT : 0u);
         any_lit |= lit;
     }
-    int stack_cap = MAX_STACK;   // as build_scene_bvh8
-    if (const char* ev = std::getenv("MPT_BVH_MAX_STACK")) stack_cap = std::max(4, std::min(MAX_STACK, std::atoi(ev)));
+    const int stack_cap = bvh_stack_cap();
     const int light_cap = std::min(MAX_STACK, c->light_bvh_max_stack);
     DBuf<uint32_t> d_mf, d_flags;
     DBuf<uint64_t> d_words, d_partial;
@@ -2306,11 +1236,10 @@ int mpt_upload_scene_mode(MptContext* c, const MptScene* s, int32_t mode, MptReb
 
 int mpt_get_bvh(MptContext* c, int which, void* nodes, int64_t nodes_cap_bytes, void* tris, int64_t tris_cap_bytes,
                 int32_t* out_counts) {
-    if (!c) return fail(MPT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->has_scene) return fail(MPT_ERR_NO_SCENE, "no scene uploaded");
+    if (const int r = need_scene(c)) return r;
     if (which != 0 && which != 1) return fail(MPT_ERR_INVALID_ARGUMENT, "bvh: which must be 0 (scene) or 1 (light)");
     if (nodes_cap_bytes < 0 || tris_cap_bytes < 0) return fail(MPT_ERR_INVALID_ARGUMENT, "bvh: bad size");
-    const bool light = c->nodes_light.p && c->tris_light.p && !c->h_light_prims.empty();
+    const bool light = has_light_tree(c);
     const DBuf<Node8>& dn = which ? c->nodes_light : c->nodes;
     const DBuf<TriRec>& dt = which ? c->tris_light : c->tris;
     const size_t nn = which && !light ? 0 : dn.n, nt = which && !light ? 0 : dt.n;

@@ -2,7 +2,7 @@
 // update before the per-triangle attribute records are made) and the host loop of the same
 // arithmetic (normals.h; DESIGN.md §2 "Geometry updates", Normals).
 //
-// Two structures with the same bytes (mpt_api.cpp: normals_fused chooses):
+// Two structures with the same bytes (mpt_geometry.cpp: normals_fused chooses):
 //   k_face + k_gather   one lane per triangle writes the face vector as a float4 to a scratch
 //                array: the indices are read coalesced, the positions gathered, as k_refit_tris
 //                does.  Then one lane per vertex walks the row of its group, gathers the 16-byte

@@ -19,7 +19,7 @@ INCLUDE = ROOT.parent / "include"
 LIB_PATH = PKG_DIR / "libmpt.so"
 OBJ_DIR = CSRC / "build"
 
-SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "image.cpp", "jpeg.cpp", "display.hip", "denoise.hip", "refit.hip", "lbvh.hip", "ploc.hip", "sah.hip", "upload.hip", "xform.hip", "skin.hip", "morph.hip", "anim.hip", "normals.hip", "temporal.hip"]
+SOURCES = ["bvh8.cpp", "mpt_kernels.hip", "bake.hip", "mpt_api.cpp", "mpt_geometry.cpp", "image.cpp", "jpeg.cpp", "display.hip", "denoise.hip", "refit.hip", "lbvh.hip", "ploc.hip", "sah.hip", "upload.hip", "xform.hip", "skin.hip", "morph.hip", "anim.hip", "normals.hip", "temporal.hip"]
 # mpt_part.hip is compiled once per part (-DMPT_TU_PART=k): the shading and ReSTIR DI kernel
 # instantiations, so that they compile in parallel with the rest
 PARTS = [1, 2, 3, 4, 5, 6, 7]
